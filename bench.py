@@ -10,9 +10,16 @@ case this script starts the N ranks itself as child processes; fewer than N visi
               2 calibrated encoder layers, each ONE fused HIP attention launch -> two CE losses + mask penalty),
               the trainer's two backward passes, gradient all-reduce (N > 1) and one Adam step.
   value     = user-sequences/sec over all ranks (weak scaling: B = 512 sequences per GPU), inputs resident in HBM.
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs DIR) and prints the
+line.  Everything else below runs only with --full (rank 0; the CPU baseline, the other shapes and the reference schedule
+on one GPU only):
+  reference_schedule = the same step with the reference's full (unpruned) schedule, a few steps after the timed ones.
   roofline  = fused calibrated-attention FORWARD kernel (contract A): algorithmic bytes per launch /
               average launch duration, measured here with HIP events over back-to-back launches on rotating
               buffer sets (> 256 MiB, so the Infinity Cache cannot serve them), against the 8 TB/s HBM3E peak.
+  roofline_ce = the three sweeps of the full-catalogue cross-entropy against the fp32 matrix peak.
+  other_configs = a few steps and the forward roofline of each of the other named shapes.
   cpu_baseline = the oracle (CPU restatement of the reference algorithm, incl. its [B,h,L,L,2dh] concatenation)
               running the same full step on the host cores; rank 0, N = 1 only.
 """
@@ -58,6 +65,12 @@ def parse():
     ap.add_argument("--layers", type=int, default=2)
     ap.add_argument("--inner", type=int, default=256)
     ap.add_argument("--items", type=int, default=None, help="catalogue size (default 100000; 20000 for --config cfg5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the timed steps: reference schedule, forward and cross-entropy "
+                         "rooflines, other named shapes, CPU baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (losses, updated parameters, gradients) "
+                         "as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short measurements of the other named shapes (L=200 d=64, configs[3], configs[4])")
@@ -86,6 +99,8 @@ def parse():
     ap.add_argument("--force-grad-sync", action="store_true",
                     help="use the data-parallel gradient path (flat buffer, graph without optimizer) even on one GPU")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     a.model = "ACSASRec"
     if a.config == "cfg4":  # "Yelp-scale synthetic, L=200 d=128 4 heads"; the catalogue size is ours (stated in the line)
         a.seq_len, a.hidden, a.heads, a.inner = 200, 128, 4, 512
@@ -438,6 +453,32 @@ def cpu_baseline(a, state_dict, steps):
                       f"{dt:.1f} s wall"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, losses):
+    """--dump-outputs: what the last timed step computed, as a caller of the trainer holds it afterwards -- the two losses
+    train_step returned, every parameter after the Adam update and every gradient of that step -- as float32 .npy files.
+    If the whole would exceed 64 MB, each of the largest arrays is replaced by a fixed seeded sample of its flattened
+    elements (the same indices on every run with the same arguments)."""
+    import numpy as np
+    arrays = {"attacked_loss": losses[0], "calibrated_loss": losses[1]}
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad
+    cap = DUMP_LIMIT_BYTES  # largest array kept whole, in bytes
+    while sum(min(4 * t.numel(), cap) for t in arrays.values()) > DUMP_LIMIT_BYTES:
+        cap //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if 4 * t.numel() > cap:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:cap // 4].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     # a process that dies in native code (a fault at teardown, an abort inside a library) leaves its Python stack on
     # stderr; together with the exit marker at the very end this turns "empty stdout" into a record of where it ended
@@ -531,7 +572,7 @@ def main():
     model.train()
     gen = torch.Generator().manual_seed(1000 + rank)
     pool = [synthetic_batch(a.batch, a.seq_len, a.items, gen, device) for _ in range(8)]
-    init_state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()} if rank == 0 else None
+    init_state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()} if rank == 0 and a.full else None
 
     if not a.no_graph:
         trainer.enable_graph(pool[0])  # capture happens before the warm-up steps; every timed step replays it
@@ -563,11 +604,13 @@ def main():
     att, cal = (float(x.detach()) for x in last)
     if not (att == att and cal == cal):
         raise SystemExit("Training loss is nan")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, model, last)  # before --full's extra steps move the parameters on
 
     # The same step with the reference's full schedule (nothing that DESIGN.md section 5 lists as provably dead is
     # skipped): reported next to `value` so that both can be judged.  Single GPU only, short, after the timed region.
     full_ms = None
-    if world == 1 and not a.no_full_schedule:
+    if a.full and world == 1 and not a.no_full_schedule:
         model.step_state.prune_dead_work = False
         try:
             full_trainer = A.AttackSASRecTrainer(A.DictConfig(learner='adam', learning_rate=1e-4), model)
@@ -598,7 +641,7 @@ def main():
             "config": {
                 "workload": (f"{a.model} full training step (spatial + adversarial calibrators, BASELINE "
                              f"configs[{ {None: 2, 'cfg2': 2, 'cfg3': 2, 'cfg4': 3, 'cfg5': 4}[a.config] }]"
-                             + ("; configs[1] spatial-only kernel under roofline_spatial_only" if a.config in (None, "cfg2", "cfg3") else "")
+                             + ("; configs[1] spatial-only kernel under roofline_spatial_only" if a.full and a.config in (None, "cfg2", "cfg3") else "")
                              + f"), synthetic {a.items}-item catalogue, B={a.batch}/GPU L={a.seq_len} d={a.hidden} "
                              f"h={a.heads} {a.layers} layers inner={a.inner}, CE loss, two-pass backward + Adam"),
                 "global_batch": world * a.batch, "seq_len": a.seq_len, "hidden": a.hidden, "heads": a.heads,
@@ -610,22 +653,23 @@ def main():
                     "ms_per_step": round(full_ms, 3), "value": round(a.batch / full_ms * 1e3, 1),
                     "note": "same step computing also the provably dead work the reference computes (DESIGN.md 5)"}},
         }
-        res["roofline"] = kernel_roofline(a, device, True, a.kernel_iters)
-        # the same kernel when every sequence has all L items ("also report the all-L worst case"): the
-        # algorithmic bytes are the same, no key tile past the last item can be skipped
-        res["roofline_full_length"] = kernel_roofline(a, device, True, a.kernel_iters, full_length=True)
-        res["roofline_spatial_only"] = kernel_roofline(a, device, False, a.kernel_iters)
-        if a.model != "AcBERT4Rec":
-            try:
-                res["roofline_ce"] = ce_roofline(a, device)
-            except Exception as e:  # (an extra of the line: never the reason a bench run fails)
-                res["roofline_ce"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and a.config is None and not a.no_other_configs and (a.batch, a.seq_len, a.hidden, a.heads) == (512, 50, 64, 2):
-            res["other_configs"] = other_configs(a, device)
-        if world == 1 and not a.no_cpu_baseline and a.model == "ACSASRec":
-            res["cpu_baseline"] = cpu_baseline(a, init_state, a.cpu_steps)
-        else:
-            res["cpu_baseline"] = None
+        if a.full:
+            res["roofline"] = kernel_roofline(a, device, True, a.kernel_iters)
+            # the same kernel when every sequence has all L items ("also report the all-L worst case"): the
+            # algorithmic bytes are the same, no key tile past the last item can be skipped
+            res["roofline_full_length"] = kernel_roofline(a, device, True, a.kernel_iters, full_length=True)
+            res["roofline_spatial_only"] = kernel_roofline(a, device, False, a.kernel_iters)
+            if a.model != "AcBERT4Rec":
+                try:
+                    res["roofline_ce"] = ce_roofline(a, device)
+                except Exception as e:  # (an extra of the line: never the reason a bench run fails)
+                    res["roofline_ce"] = {"error": f"{type(e).__name__}: {e}"[:300]}
+            if world == 1 and a.config is None and not a.no_other_configs and (a.batch, a.seq_len, a.hidden, a.heads) == (512, 50, 64, 2):
+                res["other_configs"] = other_configs(a, device)
+            if world == 1 and not a.no_cpu_baseline and a.model == "ACSASRec":
+                res["cpu_baseline"] = cpu_baseline(a, init_state, a.cpu_steps)
+            else:
+                res["cpu_baseline"] = None
         # flushed at once: stdout is a pipe or a file here (block-buffered), and a line still sitting in the buffer is
         # lost if anything goes wrong while the process is being torn down (3 of ~60 runs in this round ended with an
         # empty stdout; none of the 50 runs whose stderr was kept did)

@@ -4,12 +4,13 @@
 set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
-mkdir -p gpurun_out/r3f
-timeout -k 10 1000 python -m pytest tests -m gpu -x -q > gpurun_out/r3f/pytest_gpu.log 2>&1
+O=${1:?usage: tools/gpu_r3_final.sh OUTPUT_DIR}
+mkdir -p $O
+timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1
 rc=$?
-tail -n 4 gpurun_out/r3f/pytest_gpu.log
+tail -n 4 $O/pytest_gpu.log
 echo "pytest rc=$rc"
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python bench.py > gpurun_out/r3f/bench_line.txt 2> gpurun_out/r3f/bench_err.txt
+timeout -k 10 600 python bench.py --full > $O/bench_line.txt 2> $O/bench_err.txt
 echo "bench rc=$?"
-grep "^{" gpurun_out/r3f/bench_line.txt | cut -c1-400
+grep "^{" $O/bench_line.txt | cut -c1-400

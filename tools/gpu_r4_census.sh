@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r4/census_$tag
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o $tag -- python3 $R/bench.py "$@" --steps 12 --warmup 3 --no-cpu-baseline --no-other-configs --no-full-schedule --kernel-kinds ragged --kernel-iters 70 > $O/run.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O -o $tag -- python3 $R/bench.py "$@" --full --steps 12 --warmup 3 --no-cpu-baseline --no-other-configs --no-full-schedule --kernel-kinds ragged --kernel-iters 70 > $O/run.log 2>&1
 rc=$?
 echo "rocprof rc=$rc"
 grep "^{" $O/run.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms_per_step', d['ms_per_step'], 'value', d['value'], 'fwd', d['roofline']['avg_launch_us'], d['roofline']['frac'])"

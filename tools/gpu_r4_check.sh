@@ -10,7 +10,7 @@ rc=$?
 tail -n 15 $O/pytest_gpu.log
 echo "pytest rc=$rc"
 if [ $rc -ne 0 ]; then exit $rc; fi
-timeout -k 10 500 python bench.py > $O/bench_line.json 2> $O/bench.err
+timeout -k 10 500 python bench.py --full > $O/bench_line.json 2> $O/bench.err
 rc=$?
 echo "bench rc=$rc"; tail -c 3000 $O/bench_line.json; echo
 if [ $rc -ne 0 ]; then tail -n 20 $O/bench.err; exit $rc; fi
