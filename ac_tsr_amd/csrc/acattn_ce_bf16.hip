@@ -33,6 +33,7 @@
 #include <stdlib.h>
 
 #include "acattn_common.h"
+#include "acattn_split.h"
 
 namespace {
 
@@ -50,17 +51,11 @@ constexpr int HB_BYTES = HSLOTS * 64 * 16;
 #define CE6_PIPE 0  // vector instructions asked for behind every MFMA of a pipelined product; 0 = phases in program order
 #endif
 
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
 typedef __bf16 b4 __attribute__((ext_vector_type(4)));
 typedef short s4v __attribute__((ext_vector_type(4)));
 typedef short s8v __attribute__((ext_vector_type(8)));
 
-// product terms (plane of the first operand, plane of the second), smallest first
-#define CE6_TERMS(X) X(0, 2) X(1, 1) X(2, 0) X(0, 1) X(1, 0) X(0, 0)
-
-__device__ __forceinline__ f4 mfma_bf(const b8 a, const b8 b, const f4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
+#define CE6_TERMS(X) ACATTN_SPLIT_TERMS(X)
 
 // One wave-wide LDS-DMA: lane l copies the 16 bytes at gsrc (per lane) to LDS byte address lds_dst + 16 l (lds_dst
 // wave-uniform, in M0) without passing through registers.  Inline assembly as in acattn_fwd_dma.hip: the kernel orders
@@ -68,20 +63,6 @@ __device__ __forceinline__ f4 mfma_bf(const b8 a, const b8 b, const f4 c) {
 __device__ __forceinline__ void dma16(const void* gsrc, void* lds_dst) {
   const uint32_t lds_off = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)lds_dst;
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds_off) : "memory", "m0");
-}
-
-// x = p0 + p1 + p2 exactly (round-to-nearest pieces; v_cvt_pk_bf16_f32)
-__device__ __forceinline__ void split8(const float (&x)[8], b8& p0, b8& p1, b8& p2) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 a = (__bf16)x[j];
-    const float r1 = x[j] - (float)a;
-    const __bf16 b = (__bf16)r1;
-    const float r2 = r1 - (float)b;
-    p0[j] = a;
-    p1[j] = b;
-    p2[j] = (__bf16)r2;
-  }
 }
 
 // One workgroup per super-block of 32 batch rows: the rows' operand images.

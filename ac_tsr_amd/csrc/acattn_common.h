@@ -389,6 +389,7 @@ int acattn_launch_ce6_onehot_reduce(const acattn_ce_problem& p, const float* coe
                                     float* d_table, hipStream_t stream);
 int acattn_launch_ce6_fwd_sweep(const acattn_ce_problem& p, float2* part, void* rows_ws, int n_wg, int n_left, hipStream_t stream);
 int acattn_ce_products_choice(int mode);
+int acattn_linear_products_choice(int mode);
 int acattn_launch_dense_ce_fwd(const float* logits, int64_t rows, int64_t N, const int64_t* target, float* lse, float* row_loss,
                                hipStream_t stream);
 int acattn_launch_dense_ce_bwd(const float* logits, const float* lse, const int64_t* target, const float* coef, int64_t rows,

@@ -14,12 +14,17 @@
 // Backward: dmq_t = dmq + dqa . Waq + dgate . Wg,  dmk_t = dmk + dka . Wak,  dx = dmq_t . Wq + dmk_t . Wk + dmv . Wv
 // with the transposed weights gathered as dwords from the row-major parameters.  dmq_t / dmk_t are written because
 // they are the cotangent operands of the query / key weight gradients (acattn_linear_wgrad_grouped).
+//
+// At hidden 64 these kernels are the exact-fp32 form (acattn_linear_products(0)); by default the same chains run on
+// split bf16 products (proj_split_fwd_kernel / proj_split_bwd_kernel below).
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <type_traits>
 
 #include "acattn_common.h"
+#include "acattn_split.h"
 #include "acattn_wstage.h"
 
 namespace {
@@ -945,6 +950,268 @@ __global__ void __launch_bounds__(64 * NWV, 2) proj_staged_bwd_kernel(const acat
   }
 }
 
+// =====================================================================================================================
+// Hidden 64 on split bf16 products.  The same chains as proj_fwd_kernel / proj_bwd_kernel, every
+// product on v_mfma_f32_16x16x32_bf16 with both operands split exactly into three bf16 planes (acattn_split.h): 2 x 6
+// MFMAs of 16 cycles per 16 x 16 output tile instead of 16 fp32 MFMAs of 32.
+//   Layouts (lane = 16 g + c).  A[m = c][k = 8g + j], B[k = 8g + j][n = c], D[m = 4g + r][n = c].  The contraction of
+//   K-block s runs over the features k(s, g, j) = 32 s + 16 (j >> 2) + 4 g + (j & 3): the B operand of a lane is then
+//   registers 0..3 of accumulator tiles 2s and 2s + 1 of the product that made it (row c, features 16 t + 4 g + r), so
+//   an output feeds the next product with no shuffle, and a row read from memory in that layout is two 16-byte loads.
+//   The weights are split ONCE per workgroup: wave w splits output tile w of each matrix into the workgroup's LDS as
+//   [matrix][tile][s][plane][lane] fragments, every wave reads all of them back with ds_read_b128 (conflict-free).  The
+//   six matrices take 144 KB, so the gate (one matrix of the six) must have G <= 64 outputs; wider gates stay on
+//   proj_fwd_kernel / proj_bwd_kernel.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int SPW = 4;                                       // waves per workgroup (one per output tile)
+constexpr int SPLIT_MAT = 4 * 2 * 3 * 64;                    // b8 per matrix: [tile][s][plane][lane]
+constexpr int SPLIT_LDS = 6 * SPLIT_MAT * (int)sizeof(b8);  // bytes
+
+__device__ __forceinline__ int kperm(int s, int g, int j) { return 32 * s + 16 * (j >> 2) + 4 * g + (j & 3); }
+
+// the raw values of output tile `nt`, K-block s, of one matrix.  T = false: A[m][k] = W[m][k] (outputs m, rows past
+// n_out read as row n_out - 1 and never stored); T = true: A[m][k] = W[k][m] (the input gradient), k >= n_out zero.
+template <bool T>
+__device__ __forceinline__ void split_raw(const float* w, int n_out, int nt, int c, int g, float (&v)[2][8]) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    if constexpr (!T) {
+      const float* row = w + (size_t)min(16 * nt + c, n_out - 1) * 64 + 32 * s + 4 * g;
+      const f4 lo = *(const f4*)row, hi = *(const f4*)(row + 16);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        v[s][r] = lo[r];
+        v[s][4 + r] = hi[r];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int k = kperm(s, g, j);
+        const float t = w[(size_t)min(k, n_out - 1) * 64 + 16 * nt + c];
+        v[s][j] = k < n_out ? t : 0.f;
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ void split_store(const float (&v)[2][8], b8* mat, int nt, int lane) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    b8 p[3];
+    split8(v[s], p[0], p[1], p[2]);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) mat[((nt * 2 + s) * 3 + q) * 64 + lane] = p[q];
+  }
+}
+
+// B operand planes of rows held in accumulator layout (v[nb][t][r] = row c, feature 16 t + 4 g + r)
+template <int NB>
+__device__ __forceinline__ void split_rows(const f4 (&v)[NB][4], b8 (&b)[NB][2][3]) {
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      float x[8];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        x[r] = v[nb][2 * s][r];
+        x[4 + r] = v[nb][2 * s + 1][r];
+      }
+      split8(x, b[nb][s][0], b[nb][s][1], b[nb][s][2]);
+    }
+}
+
+// acc[nb][nt] += A(mat)[tile nt] . B[nb] for the tiles nt < NT
+template <int NB, int NT = 4>
+__device__ __forceinline__ void split_product(const b8* mat, int lane, const b8 (&b)[NB][2][3], f4 (&acc)[NB][4]) {
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    b8 a[2][3];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) a[s][q] = mat[((nt * 2 + s) * 3 + q) * 64 + lane];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) acc[nb][nt] = mfma_split(a[s], b[nb][s], acc[nb][nt]);
+  }
+}
+
+template <int NB>
+__device__ __forceinline__ Rows<NB> split_rows_of(int R, int wave) {
+  Rows<NB> w;
+  const int c = threadIdx.x & 15;
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) {
+    const int r = ((blockIdx.x * SPW + wave) * NB + nb) * 16 + c;
+    w.ok[nb] = r < R;
+    w.row[nb] = r < R ? r : R - 1;
+  }
+  return w;
+}
+
+// LDS matrices of the forward: Wq, Waq, Wg, Wk, Wak, Wv
+template <int NB>
+__global__ void __launch_bounds__(64 * SPW) proj_split_fwd_kernel(const acattn_proj_problem P, const acattn_proj_out O) {
+  extern __shared__ b8 wsp[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+  const Rows<NB> W = split_rows_of<NB>(P.rows, wave);
+  const bool gate = P.wg != nullptr;
+  {
+    const float* src[6] = {P.wq, P.waq, gate ? P.wg : P.wq, P.wk, P.wak, P.wv};
+    float v[6][2][8];
+#pragma unroll
+    for (int m = 0; m < 6; ++m) split_raw<false>(src[m], m == 2 && gate ? P.G : 64, wave, c, g, v[m]);
+#pragma unroll
+    for (int m = 0; m < 6; ++m)
+      if (m != 2 || gate) split_store(v[m], wsp + m * SPLIT_MAT, wave, lane);
+  }
+  f4 xb[NB][4], m[NB][4], acc[NB][4];
+  b8 xs[NB][2][3], ms[NB][2][3];
+  f4 bias[4];
+  load_rows<4, NB>(P.x, W, g, xb);
+  load_bias<4>(P.bq, g, bias);
+  __syncthreads();
+  split_rows<NB>(xb, xs);
+  set_rows<4, NB>(bias, m);
+  split_product<NB>(wsp, lane, xs, m);  // mq
+  store_rows<4, NB>(O.mq, W, g, m);
+  if (O.affine) write_affine<4, NB>(m, W, P, O.affine, 0, P.b_order[0], P.b_dist[0], 0, c, g);
+  split_rows<NB>(m, ms);
+  load_bias<4>(P.baq, g, bias);
+  set_rows<4, NB>(bias, acc);
+  split_product<NB>(wsp + SPLIT_MAT, lane, ms, acc);  // qa
+  store_rows<4, NB>(O.qa, W, g, acc);
+  if (gate) {
+    const int GT = (P.G + 15) >> 4;  // 1 .. 4
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      f4 b;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) b[r] = P.bg[min(16 * nt + 4 * g + r, P.G - 1)];
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) acc[nb][nt] = b;
+    }
+    split_product<NB>(wsp + 2 * SPLIT_MAT, lane, ms, acc);  // gate logits (tiles past G are computed and dropped)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      if (nt >= GT) break;
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        f4 v = acc[nb][nt];
+        if (O.gate_prob) v = gate_value(v, 0);  // sigmoid once per (b, i, j): the heads share it (layers.py:887)
+        const int j0 = 16 * nt + 4 * g;
+        float* dst = O.gate + (size_t)W.row[nb] * P.G + j0;
+        if (W.ok[nb] && j0 + 3 < P.G) {
+          *(f4u*)dst = v;
+        } else if (W.ok[nb]) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (j0 + r < P.G) dst[r] = v[r];
+        }
+      }
+    }
+  }
+  load_bias<4>(P.bk, g, bias);
+  set_rows<4, NB>(bias, m);
+  split_product<NB>(wsp + 3 * SPLIT_MAT, lane, xs, m);  // mk
+  store_rows<4, NB>(O.mk, W, g, m);
+  if (O.affine) write_affine<4, NB>(m, W, P, O.affine, 64 / P.n_heads, 0.f, 0.f, 2, c, g);
+  split_rows<NB>(m, ms);
+  load_bias<4>(P.bak, g, bias);
+  set_rows<4, NB>(bias, acc);
+  split_product<NB>(wsp + 4 * SPLIT_MAT, lane, ms, acc);  // ka
+  store_rows<4, NB>(O.ka, W, g, acc);
+  load_bias<4>(P.bv, g, bias);
+  set_rows<4, NB>(bias, acc);
+  split_product<NB>(wsp + 5 * SPLIT_MAT, lane, xs, acc);  // mv
+  store_rows<4, NB>(O.mv, W, g, acc);
+}
+
+// LDS matrices of the backward (transposed): Waq, Wg, Wq, Wak, Wk, Wv.  MODE as in proj_bwd_kernel.
+template <int NB, int MODE>
+__global__ void __launch_bounds__(64 * SPW) proj_split_bwd_kernel(const acattn_proj_problem P, const acattn_proj_bwd_io IO) {
+  extern __shared__ b8 wsp[];
+  const bool h_dmq = MODE == 1 || (MODE == 0 && IO.dmq), h_dmk = MODE == 1 || (MODE == 0 && IO.dmk);
+  const bool h_dmv = MODE == 1 || (MODE == 0 && IO.dmv);
+  const bool h_dqa = MODE != 0 || IO.dqa, h_dka = MODE != 0 || IO.dka, h_dx = MODE != 0 || IO.dx;
+  const bool h_qt = MODE != 0 || IO.dmq_total, h_kt = MODE != 0 || IO.dmk_total;
+  const bool gate = MODE != 2 && IO.dgate && P.wg;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+  const Rows<NB> W = split_rows_of<NB>(P.rows, wave);
+  {
+    const float* src[6] = {P.waq, gate ? P.wg : P.waq, P.wq, P.wak, P.wk, P.wv};
+    const bool need[6] = {h_dqa, gate, h_dx, h_dka, h_dx, h_dx && h_dmv};
+    float v[6][2][8];
+#pragma unroll
+    for (int m = 0; m < 6; ++m)
+      if (need[m]) split_raw<true>(src[m], m == 1 ? P.G : 64, wave, c, g, v[m]);
+#pragma unroll
+    for (int m = 0; m < 6; ++m)
+      if (need[m]) split_store(v[m], wsp + m * SPLIT_MAT, wave, lane);
+  }
+  auto zero = [&](f4 (&v)[NB][4]) {
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) v[nb][t] = f4{0.f, 0.f, 0.f, 0.f};
+  };
+  f4 in[NB][4], dq[NB][4], dk[NB][4], dx[NB][4];
+  b8 bs[NB][2][3];
+  if (IO.dx_init && h_dx) load_rows<4, NB>(IO.dx_init, W, g, dx); else zero(dx);  // the residual path's share of dx
+  if (h_dmq) load_rows<4, NB>(IO.dmq, W, g, dq); else zero(dq);
+  if (h_dqa) load_rows<4, NB>(IO.dqa, W, g, in);
+  __syncthreads();
+
+  // ---- d mq (total) = dmq + dqa . Waq + dgate . Wg;  dx += d mq . Wq ------------------------------------------------
+  if (h_dqa) {
+    split_rows<NB>(in, bs);
+    split_product<NB>(wsp, lane, bs, dq);
+  }
+  if (gate) {
+    // B[k][row c] = dgate[row][k], k = kperm(s, g, j) < G (G <= 64; rows of G floats: dword reads)
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        float x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int k = kperm(s, g, j);
+          const float t = IO.dgate[(size_t)W.row[nb] * P.G + min(k, P.G - 1)];
+          x[j] = k < P.G ? t : 0.f;
+        }
+        split8(x, bs[nb][s][0], bs[nb][s][1], bs[nb][s][2]);
+      }
+    split_product<NB>(wsp + SPLIT_MAT, lane, bs, dq);
+  }
+  if (h_qt) store_rows<4, NB>(IO.dmq_total, W, g, dq);
+  if (h_dx) {
+    split_rows<NB>(dq, bs);
+    split_product<NB>(wsp + 2 * SPLIT_MAT, lane, bs, dx);
+  }
+
+  // ---- d mk (total) = dmk + dka . Wak;  dx += d mk . Wk + d mv . Wv ---------------------------------------------------
+  if (h_dmk) load_rows<4, NB>(IO.dmk, W, g, dk); else zero(dk);
+  if (h_dka) {
+    load_rows<4, NB>(IO.dka, W, g, in);
+    split_rows<NB>(in, bs);
+    split_product<NB>(wsp + 3 * SPLIT_MAT, lane, bs, dk);
+  }
+  if (h_kt) store_rows<4, NB>(IO.dmk_total, W, g, dk);
+  if (h_dx) {
+    split_rows<NB>(dk, bs);
+    split_product<NB>(wsp + 4 * SPLIT_MAT, lane, bs, dx);
+    if (h_dmv) {
+      load_rows<4, NB>(IO.dmv, W, g, in);
+      split_rows<NB>(in, bs);
+      split_product<NB>(wsp + 5 * SPLIT_MAT, lane, bs, dx);
+    }
+    store_rows<4, NB>(IO.dx, W, g, dx);
+  }
+}
+
 int rows_per_wave(int rows) {
   static const int forced = getenv("ACATTN_PROJ_ROWS_PER_WAVE") ? atoi(getenv("ACATTN_PROJ_ROWS_PER_WAVE")) : 0;  // measurements
   if (forced == 16 || forced == 32) return forced;
@@ -1026,10 +1293,55 @@ int launch_wide_bwd(const acattn_proj_problem& p, const acattn_proj_bwd_io& io, 
 }
 }  // namespace
 
+namespace {
+// g_linear_products: 0 = exact fp32 MFMA everywhere (acattn_linear_products, or ACATTN_LINEAR_PRODUCTS=fp32), 1 = the
+// hidden-64 projections on split bf16 products (gates up to 64 outputs; the default)
+int g_linear_products = -1;
+int linear_products() {
+  if (g_linear_products < 0) {
+    const char* e = getenv("ACATTN_LINEAR_PRODUCTS");
+    g_linear_products = e && !strcmp(e, "fp32") ? 0 : 1;
+  }
+  return g_linear_products;
+}
+bool use_split(const acattn_proj_problem& p) { return p.H == 64 && (!p.wg || p.G <= 64) && linear_products() == 1; }
+
+// the dynamic LDS of a split kernel is above the 64 KB default: raised once per kernel
+template <class K>
+bool allow_split_lds(K kern) {
+  return hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_LDS) == hipSuccess;
+}
+
+template <int NB>
+int launch_split_fwd(const acattn_proj_problem& p, const acattn_proj_out& o, hipStream_t stream) {
+  static const bool lds_ok = allow_split_lds(proj_split_fwd_kernel<NB>);
+  if (!lds_ok) return (int)hipErrorInvalidValue;
+  const int wgs = (p.rows + 16 * NB * SPW - 1) / (16 * NB * SPW);
+  hipLaunchKernelGGL((proj_split_fwd_kernel<NB>), dim3(wgs), dim3(64 * SPW), SPLIT_LDS, stream, p, o);
+  return (int)hipGetLastError();
+}
+
+template <int NB, int MODE>
+int launch_split_bwd(const acattn_proj_problem& p, const acattn_proj_bwd_io& io, hipStream_t stream) {
+  static const bool lds_ok = allow_split_lds(proj_split_bwd_kernel<NB, MODE>);
+  if (!lds_ok) return (int)hipErrorInvalidValue;
+  const int wgs = (p.rows + 16 * NB * SPW - 1) / (16 * NB * SPW);
+  hipLaunchKernelGGL((proj_split_bwd_kernel<NB, MODE>), dim3(wgs), dim3(64 * SPW), SPLIT_LDS, stream, p, io);
+  return (int)hipGetLastError();
+}
+}  // namespace
+
+int acattn_linear_products_choice(int mode) {
+  const int old = linear_products();
+  if (mode >= 0 && mode <= 1) g_linear_products = mode;
+  return old;
+}
+
 int acattn_launch_proj_fwd(const acattn_proj_problem& p, const acattn_proj_out& o, hipStream_t stream) {
   if (p.H == 128) return launch_wide_fwd<128>(p, o, stream);
   if (p.H == 256) return launch_wide_fwd<256>(p, o, stream);
   const int rpw = rows_per_wave(p.rows), blocks = (p.rows + rpw - 1) / rpw;
+  if (use_split(p)) return rpw == 32 ? launch_split_fwd<2>(p, o, stream) : launch_split_fwd<1>(p, o, stream);
   if (rpw == 32)
     hipLaunchKernelGGL((proj_fwd_kernel<64, 2>), dim3(blocks), dim3(64), 0, stream, p, o);
   else
@@ -1045,6 +1357,16 @@ int acattn_launch_proj_bwd(const acattn_proj_problem& p, const acattn_proj_bwd_i
   const bool all_in = attack && io.dmq && io.dmk && io.dmv && (io.dgate || !p.wg);
   const bool attack_only = attack && !io.dmq && !io.dmk && !io.dmv && !io.dgate;
   const int mode = !outs ? 0 : all_in ? 1 : attack_only ? 2 : 0;
+  if (use_split(p)) {
+    if (rpw == 32) {
+      if (mode == 1) return launch_split_bwd<2, 1>(p, io, stream);
+      if (mode == 2) return launch_split_bwd<2, 2>(p, io, stream);
+      return launch_split_bwd<2, 0>(p, io, stream);
+    }
+    if (mode == 1) return launch_split_bwd<1, 1>(p, io, stream);
+    if (mode == 2) return launch_split_bwd<1, 2>(p, io, stream);
+    return launch_split_bwd<1, 0>(p, io, stream);
+  }
 #define LAUNCH(NB, MODE) hipLaunchKernelGGL((proj_bwd_kernel<64, NB, MODE>), dim3(blocks), dim3(64), 0, stream, p, io)
   if (rpw == 32) {
     if (mode == 1) LAUNCH(2, 1); else if (mode == 2) LAUNCH(2, 2); else LAUNCH(2, 0);

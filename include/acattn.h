@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ACATTN_ABI_VERSION 29
+#define ACATTN_ABI_VERSION 30
 
 /* attention-mask encodings (recbole/model/abstract_recommender.py:136-143 builds the dense form) */
 enum {
@@ -536,6 +536,15 @@ int acattn_projections_supported(int32_t H, int32_t G);
 int64_t acattn_projections_bwd_workspace_bytes(const acattn_proj_problem* p);
 int acattn_projections_fwd(const acattn_proj_problem* p, const acattn_proj_out* out, void* stream);
 int acattn_projections_bwd(const acattn_proj_problem* p, const acattn_proj_bwd_io* io, void* stream);
+
+/* ABI 30: arithmetic of the hidden-64 projection products (acattn_projections_fwd / _bwd).  ACATTN_LINEAR_PRODUCTS_FP32:
+ * the exact-fp32 matrix instruction; ACATTN_LINEAR_PRODUCTS_DEFAULT: bf16 matrix instructions on operands split exactly
+ * into three bf16 planes (six products per pair, as accurate as fp32: DESIGN.md 4.6) wherever the gate has at most 64
+ * outputs.  Hidden 128 / 256 always use fp32.  The environment variable ACATTN_LINEAR_PRODUCTS=fp32 sets the initial mode.
+ * Process-wide; returns the previous mode; any other value only queries. */
+#define ACATTN_LINEAR_PRODUCTS_FP32 0
+#define ACATTN_LINEAR_PRODUCTS_DEFAULT 1
+int acattn_linear_products(int mode);
 
 /*
  * torch.optim.Adam's update (the reference's optimizer: recbole/trainer/trainer.py:590-615, `learner: adam`) for up to
