@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("ACATTN_LIB") or os.path.join(CSRC, "libacattn.so")  # ACATTN_LIB: experiments only
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "acattn.h")
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 MAX_MASKS = 8  # ACATTN_MAX_MASKS
 NSTAT = 8
 MASK_STRUCTURED, MASK_DENSE_LL, MASK_DENSE_L = 0, 1, 2
@@ -106,7 +106,7 @@ class TailProblem(C.Structure):
                 ("g1", _f), ("b1", _f), ("w1", _f), ("bb1", _f), ("w2", _f), ("bb2", _f), ("g2", _f), ("b2", _f),
                 ("eps1", C.c_float), ("eps2", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("keep1", _f),
                 ("keep2", _f), ("seed1", C.c_uint64), ("seed2", C.c_uint64), ("seed_device", _f), ("src_index", _f),
-                ("src_R", C.c_int32), ("src_L", C.c_int32)]
+                ("src_R", C.c_int32), ("src_L", C.c_int32), ("split_planes", _f)]
 
 
 class TailSaved(C.Structure):
@@ -162,6 +162,8 @@ SYMBOLS = {
     "acattn_layer_tail_bwd_partial_rows_for": (C.c_int32, [C.c_int32, C.c_int32]),
     "acattn_layer_tail_bwd_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "acattn_select_layer_tail_blocks": (C.c_int, [C.c_int]),
+    "acattn_layer_tail_split_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "acattn_layer_tail_split_weights": (C.c_int, [C.POINTER(TailProblem), C.c_void_p, C.c_void_p]),
     "acattn_adam_step": (C.c_int, [C.POINTER(AdamGroup), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _f,
                                    C.c_void_p]),
     "acattn_dense_ce_fwd": (C.c_int, [_f, C.c_int64, C.c_int64, _f, _f, _f, C.c_void_p]),

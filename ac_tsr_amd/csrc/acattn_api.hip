@@ -265,6 +265,8 @@ static int check_tail(const acattn_tail_problem* p, const acattn_tail_saved* s) 
   if (!(p->p1 >= 0.f && p->p1 < 1.f) || !(p->p2 >= 0.f && p->p2 < 1.f)) return fail("dropout probabilities must be in [0, 1)");
   if (!s->h1 || !s->st1 || !s->a || !s->h3 || !s->st2) return fail("layer tail: saved tensors must be non-NULL");
   if (p->src_index && (p->src_R < 1 || p->src_L < 1)) return fail("layer tail: src_index needs src_R, src_L >= 1");
+  if (p->split_planes && p->H != 64) return fail("layer tail: split_planes is for hidden 64 only");
+  if (((uintptr_t)p->split_planes & 15) != 0) return fail("layer tail: split_planes must be 16-byte aligned");
   return 0;
 }
 
@@ -274,6 +276,19 @@ int32_t acattn_layer_tail_bwd_partial_rows(int32_t rows) { return acattn_tail_bw
 int32_t acattn_layer_tail_bwd_partial_rows_for(int32_t rows, int32_t H) { return acattn_tail_bwd_partial_rows_h(rows, H); }
 int64_t acattn_layer_tail_bwd_workspace_bytes(int32_t H, int32_t I) {
   return acattn_tail_supported(H, I) ? acattn_tail_bwd_ws_bytes(H, I) : -1;
+}
+
+int64_t acattn_layer_tail_split_bytes(int32_t H, int32_t I, int32_t rows) {
+  return acattn_tail_supported(H, I) && rows > 0 ? acattn_tail_split_bytes(H, I, rows) : 0;
+}
+
+int acattn_layer_tail_split_weights(const acattn_tail_problem* p, void* planes, void* stream) {
+  if (!p || !planes || !p->wd || !p->w1 || !p->w2) return fail("layer tail split planes: problem, weights and planes must be non-NULL");
+  if (p->H != 64 || (p->I != 256 && p->I != 128)) return fail("layer tail split planes: hidden 64, inner 256 or 128 only");
+  if (((uintptr_t)planes & 15) != 0) return fail("layer tail split planes: planes must be 16-byte aligned");
+  const int rc = acattn_launch_tail_split(*p, planes, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
 }
 
 int acattn_select_layer_tail_blocks(int nb) {

@@ -32,14 +32,22 @@
 // leave the critical SIMD with two blocks.  Without the stores 37.5 us, without GELU 34.0, without both 33.7, with the
 // weight fragments always hitting L1 31.4: neither HBM nor L2 is the limit.
 //
+// Hidden 64, default [r6]: the per-wave and four-wave forms run as tail_split_fwd_kernel / tail_split_bwd_kernel, the same
+// chains with every product as six bf16 MFMAs on exactly split operands (acattn_split.h), the weights read as planes
+// that tail_split_planes_kernel wrote (acattn_tail_problem.split_planes).  Measured (25,600 / 512 rows):
+// forward 34.7 / 10.7 us, backward 40.4 / 16.0 us.  acattn_linear_products(0) or ACATTN_TAIL_PRODUCTS=fp32 (the tails
+// alone) bring the fp32 kernels back; the staged form and hidden 128 / 256 are always fp32.
+//
 // Dropout decisions: row_keep_scale() of acattn_rowops.h, i.e. exactly those of acattn_ln.hip for the same
 // (seed, row, column): the fused and the unfused formulation are interchangeable between forward and backward.
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 
 #include "acattn_common.h"
 #include "acattn_rowops.h"
+#include "acattn_split.h"
 #include "acattn_wstage.h"
 
 int acattn_tail_bwd_partial_rows(int rows);
@@ -562,6 +570,432 @@ __global__ void __launch_bounds__(64 * NW) tail_bwd_kernel(const acattn_tail_pro
   }
 }
 
+
+// =====================================================================================================================
+// Hidden 64 on split bf16 products (the default).  The same chains as tail_fwd_kernel / tail_bwd_kernel
+// with every product on v_mfma_f32_16x16x32_bf16, both operands split exactly into three bf16 planes (acattn_split.h):
+// 6 MFMAs of 16 cycles per 16 x 16 x 32 block instead of 8 fp32 MFMAs of 32.  LayerNorm, GELU, dropout, residuals,
+// statistics and the LayerNorm partials are the fp32 code above; what the kernels write has the same meaning and layout.
+//   Layouts (lane = 16 g + c) as the split projections (acattn_proj.hip): A[m = c][k = 8g + j], B[k = 8g + j][n = c],
+//   D[m = 4g + r][n = c], K-block s over the features kperm(s, g, j) = 32 s + 16 (j >> 2) + 4 g + (j & 3), so a lane's
+//   B operand of K-block s is registers 0..3 of accumulator tiles 2s and 2s + 1.  The inner dimension is therefore
+//   walked in PAIRS of 16-column slabs (one K-block of dense_2 / of the backward's dense_1^T).
+//   The weights are not split here: tail_split_planes_kernel writes them once per forward node (acattn_layer_tail_split_
+//   weights) as 16-byte fragments in the order the kernels load them, [mt][s][plane][lane], forward (A = W) and
+//   transposed for the backward (A[m][k] = W[k][m]: contiguous loads instead of the fp32 kernel's dword gathers).
+// ---------------------------------------------------------------------------------------------------------------------
+template <int I>
+struct TailPlanes {  // offsets in b8 of the planes buffer (acattn_tail_problem.split_planes)
+  static constexpr int SQ = 64 * 64 * 3 / 8, RECT = I * 64 * 3 / 8;  // one 64 x 64 / one I x 64 matrix, three planes
+  static constexpr int FWD_D = 0, FWD_1 = SQ, FWD_2 = SQ + RECT;      // Wd, W1 [I][64], W2 [64][I]
+  static constexpr int BWD_D = SQ + 2 * RECT, BWD_1 = 2 * SQ + 2 * RECT, BWD_2 = 2 * SQ + 3 * RECT;  // Wd^T, W1^T, W2^T
+  static constexpr int TOTAL = 2 * SQ + 4 * RECT;
+};
+
+// Accuracy: against fp64 the bf16 MFMA's sums have a negative mean error (rounding toward -inf inside the instruction;
+// 25,600 rows, h3: mean error -1.35e-7 at a mean absolute error of 2.1e-7, where the fp32 kernels' mean is 3e-9).
+// Per element the split products are closer to fp64 than the fp32 kernels; in sums over many rows (the bias and
+// LayerNorm gradients) the bias adds up to about four times the fp32 kernels' error.  Starting every K-block from a
+// zero accumulator and adding it with a rounding VALU add does not remove it (mean error -1.76e-7) and spills.
+__device__ __forceinline__ int tail_kperm(int s, int g, int j) { return 32 * s + 16 * (j >> 2) + 4 * g + (j & 3); }
+
+// one thread per 16-byte fragment of one matrix (blockIdx.y: Wd, W1, W2, Wd^T, W1^T, W2^T): A[m][k] = W[m][k] or W[k][m]
+template <int I>
+__global__ void __launch_bounds__(256) tail_split_planes_kernel(const float* wd, const float* w1, const float* w2, b8* planes) {
+  using L = TailPlanes<I>;
+  const int mtx = blockIdx.y, which = mtx % 3;
+  const bool T = mtx >= 3;
+  const float* w = which == 0 ? wd : which == 1 ? w1 : w2;
+  const int M = which == 0 ? 64 : ((which == 1) != T ? I : 64), K = (which == 0 ? 64 * 64 : 64 * I) / M, KS = K / 32;
+  b8* dst = planes + (mtx == 0 ? L::FWD_D : mtx == 1 ? L::FWD_1 : mtx == 2 ? L::FWD_2 : mtx == 3 ? L::BWD_D : mtx == 4 ? L::BWD_1 : L::BWD_2);
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (M / 16) * KS * 64) return;
+  const int lane = idx & 63, f = idx >> 6, mt = f / KS, s = f % KS, c = lane & 15, g = lane >> 4, m = 16 * mt + c;
+  float x[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int k = tail_kperm(s, g, j);
+    x[j] = T ? w[(size_t)k * M + m] : w[(size_t)m * K + k];
+  }
+  b8 p[3];
+  split8(x, p[0], p[1], p[2]);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) dst[((size_t)f * 3 + q) * 64 + lane] = p[q];
+}
+
+// the three planes of fragment (mt, s) of a plane matrix with KS K-blocks
+template <int KS>
+__device__ __forceinline__ void load_frag(const b8* mat, int mt, int s, int lane, b8 (&a)[3]) {
+#pragma unroll
+  for (int q = 0; q < 3; ++q) a[q] = mat[((mt * KS + s) * 3 + q) * 64 + lane];
+}
+
+// B operand planes of the K-block made of accumulator tiles lo, hi (row c, features 16 t + 4 g + r of tiles 2s, 2s + 1)
+__device__ __forceinline__ void split_tiles(const f4 lo, const f4 hi, b8 (&b)[3]) {
+  float x[8];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    x[r] = lo[r];
+    x[4 + r] = hi[r];
+  }
+  split8(x, b[0], b[1], b[2]);
+}
+
+template <int NB>
+__device__ __forceinline__ void split_rows64(const f4 (&v)[NB][4], b8 (&b)[NB][2][3]) {
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) split_tiles(v[nb][2 * s], v[nb][2 * s + 1], b[nb][s]);
+}
+
+// acc[nb][nt] += A(mat)[tile nt] . B[nb] over the two K-blocks of a 64-wide contraction, for the four output tiles
+template <int NB>
+__device__ __forceinline__ void split_square(const b8* mat, int lane, const b8 (&b)[NB][2][3], f4 (&acc)[NB][4]) {
+#pragma unroll
+  for (int nt = 0; nt < 4; ++nt)
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      b8 w[3];
+      load_frag<2>(mat, nt, s, lane, w);
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) acc[nb][nt] = mfma_split(w, b[nb][s], acc[nb][nt]);
+    }
+}
+
+// NB, NW and the row blocks as tail_fwd_kernel; wave `wave` of NW takes the slab pairs wave, wave + NW, ...
+template <int H, int I, int NB, int NW = 1>
+__global__ void __launch_bounds__(64 * NW) tail_split_fwd_kernel(const acattn_tail_problem P, const acattn_tail_saved S) {
+  static_assert(H == 64 && (NW == 1 || NB == 1), "hidden 64; the slab split works on one row block");
+  using L = TailPlanes<I>;
+  constexpr int DT = 4, NP = I / 32, NJ = NP / NW;  // slab pairs, per wave
+  static_assert(NP % NW == 0 && NJ >= 1, "whole pairs per wave");
+  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+  const int wave = NW > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
+  const Rows<NB> W = wave_rows<NB>(P);
+  const uint64_t step = P.seed_device ? *P.seed_device : 0ull;
+  const b8* planes = (const b8*)P.split_planes;
+  const b8 *pw1 = planes + L::FWD_1, *pw2 = planes + L::FWD_2;
+
+  // dense_1 fragments of slab pair j (tiles 2p, 2p + 1, both K-blocks) and its bias
+  struct W1Pair {
+    b8 w[2][2][3];
+    f4 b[2];
+  };
+  auto load_w1 = [&](int p, W1Pair& d) {
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) load_frag<2>(pw1, 2 * p + tt, s, lane, d.w[tt][s]);
+      d.b[tt] = *(const f4*)(P.bb1 + 32 * p + 16 * tt + 4 * g);
+    }
+  };
+  W1Pair w1b[2];
+  load_w1(wave, w1b[0]);
+
+  // ---- h1 = dense(ctx) + bias;  a = LayerNorm(dropout(h1) + x) ---------------------------------------------------------
+  f4 h1[NB][DT], a[NB][DT];
+  {
+    f4 cb[NB][DT], res[NB][DT], bd[DT], g1[DT], b1[DT];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        cb[nb][t] = *(const f4*)(P.ctx + (size_t)W.src[nb] * H + 16 * t + 4 * g);
+        res[nb][t] = *(const f4*)(P.x + (size_t)W.src[nb] * H + 16 * t + 4 * g);
+      }
+    load_cols<DT>(P.bd, g, bd);
+    load_cols<DT>(P.g1, g, g1);
+    load_cols<DT>(P.b1, g, b1);
+    b8 cs[NB][2][3];
+    split_rows64<NB>(cb, cs);
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int nt = 0; nt < DT; ++nt) h1[nb][nt] = bd[nt];
+    split_square<NB>(planes + L::FWD_D, lane, cs, h1);
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      f4 keep[DT];
+#pragma unroll
+      for (int t = 0; t < DT; ++t) keep[t] = row_keep_scale(P.p1, P.keep1, P.seed1 + step, W.row[nb], 4 * t + g, H);
+      float mean, rstd;
+      ln_forward<DT>(h1[nb], res[nb], keep, g1, b1, P.eps1, a[nb], mean, rstd);
+      if (W.ok[nb] && wave == 0) {
+#pragma unroll
+        for (int t = 0; t < DT; ++t) {
+          const size_t o = (size_t)W.row[nb] * H + 16 * t + 4 * g;
+          *(f4*)(S.h1 + o) = h1[nb][t];
+          *(f4*)(S.a + o) = a[nb][t];
+        }
+        if (g == 0) *(float2*)(S.st1 + 2 * (size_t)W.row[nb]) = float2{mean, rstd};
+      }
+    }
+  }
+
+  // ---- h3 = dense_2(gelu(dense_1(a))), one pair of 16-column slabs at a time ---------------------------------------------
+  // Step j: request dense_2's fragments of pair j and dense_1's of pair j + 1; products of pair j; GELU; dense_2.
+  b8 as[NB][2][3];
+  split_rows64<NB>(a, as);
+  f4 h3[NB][DT];
+#pragma unroll
+  for (int nt = 0; nt < DT; ++nt) {
+    const f4 bb2 = *(const f4*)(P.bb2 + 16 * nt + 4 * g);
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) h3[nb][nt] = wave == 0 ? bb2 : f4{0.f, 0.f, 0.f, 0.f};
+  }
+  static_for<NJ>([&](auto jc) {
+    constexpr int J = decltype(jc)::value;
+    const int p = wave + NW * J;
+    b8 w2[DT][3];
+#pragma unroll
+    for (int nt = 0; nt < DT; ++nt) load_frag<NP>(pw2, nt, p, lane, w2[nt]);
+    if constexpr (J + 1 < NJ) load_w1(p + NW, w1b[(J + 1) & 1]);
+    PIN_ORDER();
+    const W1Pair& cur = w1b[J & 1];
+    f4 h2[NB][2];
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) h2[nb][tt] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) h2[nb][tt] = mfma_split(cur.w[tt][s], as[nb][s], h2[nb][tt]);
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      f4 act[2];
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt) {
+        const f4 pre = h2[nb][tt] + cur.b[tt];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) act[tt][r] = gelu_erf(pre[r]);
+        if (W.ok[nb]) *(f4*)(S.act + (size_t)W.row[nb] * I + 32 * p + 16 * tt + 4 * g) = act[tt];
+      }
+      b8 ap[3];
+      split_tiles(act[0], act[1], ap);
+#pragma unroll
+      for (int nt = 0; nt < DT; ++nt) h3[nb][nt] = mfma_split(w2[nt], ap, h3[nb][nt]);
+    }
+    PIN_ORDER();
+  });
+
+  if (NW > 1) {  // fold the waves' partial products into wave 0
+    __shared__ f4 red[NW > 1 ? NW - 1 : 1][DT][64];
+    if (wave > 0) {
+#pragma unroll
+      for (int t = 0; t < DT; ++t) red[wave - 1][t][lane] = h3[0][t];
+    }
+    __syncthreads();
+    if (wave > 0) return;
+#pragma unroll
+    for (int w = 0; w < NW - 1; ++w)
+#pragma unroll
+      for (int t = 0; t < DT; ++t) h3[0][t] += red[w][t][lane];
+  }
+
+  // ---- out = LayerNorm(dropout(h3) + a) -------------------------------------------------------------------------
+  f4 g2[DT], b2[DT];
+  load_cols<DT>(P.g2, g, g2);
+  load_cols<DT>(P.b2, g, b2);
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb) {
+    f4 keep[DT], y[DT];
+#pragma unroll
+    for (int t = 0; t < DT; ++t) keep[t] = row_keep_scale(P.p2, P.keep2, P.seed2 + step, W.row[nb], 4 * t + g, H);
+    float mean, rstd;
+    ln_forward<DT>(h3[nb], a[nb], keep, g2, b2, P.eps2, y, mean, rstd);
+    if (W.ok[nb]) {
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        const size_t o = (size_t)W.row[nb] * H + 16 * t + 4 * g;
+        *(f4*)(S.h3 + o) = h3[nb][t];
+        *(f4*)(S.out + o) = y[t];
+      }
+      if (g == 0) *(float2*)(S.st2 + 2 * (size_t)W.row[nb]) = float2{mean, rstd};
+    }
+  }
+}
+
+template <int H, int I, int NB, int NW = 1>
+__global__ void __launch_bounds__(64 * NW) tail_split_bwd_kernel(const acattn_tail_problem P, const acattn_tail_saved S,
+                                                                 const acattn_tail_bwd_io IO) {
+  static_assert(H == 64 && (NW == 1 || NB == 1), "hidden 64; the slab split works on one row block");
+  using L = TailPlanes<I>;
+  constexpr int DT = 4, NP = I / 32, NJ = NP / NW;
+  static_assert(NP % NW == 0 && NJ >= 1, "whole pairs per wave");
+  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+  const int wave = NW > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
+  const Rows<NB> W = wave_rows<NB>(P);
+  const uint64_t step = P.seed_device ? *P.seed_device : 0ull;
+  float* part = IO.dgb_part ? IO.dgb_part + (size_t)blockIdx.x * 4 * H : nullptr;
+  const b8* planes = (const b8*)P.split_planes;
+  const b8 *pw1 = planes + L::FWD_1, *pw1t = planes + L::BWD_1, *pw2t = planes + L::BWD_2;
+
+  // dense_1 (rebuilds h2) and dense_2^T fragments of slab pair p, and dense_1's bias
+  struct Pair {
+    b8 w1[2][2][3], w2t[2][2][3];
+    f4 b[2];
+  };
+  auto load_pair = [&](int p, Pair& d) {
+#pragma unroll
+    for (int tt = 0; tt < 2; ++tt) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        load_frag<2>(pw1, 2 * p + tt, s, lane, d.w1[tt][s]);
+        load_frag<2>(pw2t, 2 * p + tt, s, lane, d.w2t[tt][s]);
+      }
+      d.b[tt] = *(const f4*)(P.bb1 + 32 * p + 16 * tt + 4 * g);
+    }
+  };
+  Pair pb[2];
+  load_pair(wave, pb[0]);
+
+  // ---- through the second LayerNorm: d h3 (after the dropout), d a (residual share) -------------------------------
+  f4 a[NB][DT], dh3[NB][DT], da[NB][DT];
+  {
+    f4 acc_g[DT], acc_b[DT];
+#pragma unroll
+    for (int t = 0; t < DT; ++t) acc_g[t] = acc_b[t] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      f4 z[DT], keep[DT], dy[DT];
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        const size_t o = (size_t)W.row[nb] * H + 16 * t + 4 * g;
+        z[t] = *(const f4*)(S.h3 + o);
+        a[nb][t] = *(const f4*)(S.a + o);
+        dy[t] = *(const f4*)(IO.d_out + o);
+        keep[t] = row_keep_scale(P.p2, P.keep2, P.seed2 + step, W.row[nb], 4 * t + g, H);
+      }
+      const float2 st = *(const float2*)(S.st2 + 2 * (size_t)W.row[nb]);
+      ln_backward<DT>(z, a[nb], keep, P.g2, st.x, st.y, dy, W.ok[nb], g, da[nb], acc_g, acc_b);
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        dh3[nb][t] = da[nb][t] * keep[t];
+        if (IO.d_h3 && W.ok[nb] && wave == 0) *(f4*)(IO.d_h3 + (size_t)W.row[nb] * H + 16 * t + 4 * g) = dh3[nb][t];
+        if (wave > 0) da[nb][t] = f4{0.f, 0.f, 0.f, 0.f};  // the residual share of d a travels with wave 0
+      }
+    }
+    if (part && wave == 0) {
+      store_partial<DT>(part + 2 * H, acc_g, c, g);
+      store_partial<DT>(part + 3 * H, acc_b, c, g);
+    }
+  }
+
+  // ---- d a += W1^T (gelu'(h2) * (W2^T d h3)), one slab pair at a time; h2 rebuilt from a ---------------------------
+  // Step j: request dense_1^T's fragments of pair j and the pair fragments of pair j + 1; h2 and d act; GELU'; d a.
+  {
+    b8 as[NB][2][3], ds[NB][2][3];
+    split_rows64<NB>(a, as);
+    split_rows64<NB>(dh3, ds);
+    static_for<NJ>([&](auto jc) {
+      constexpr int J = decltype(jc)::value;
+      const int p = wave + NW * J;
+      b8 w1t[DT][3];  // A[k = 16 nt + c][m = inner of K-block p] = W1[m][k]
+#pragma unroll
+      for (int nt = 0; nt < DT; ++nt) load_frag<NP>(pw1t, nt, p, lane, w1t[nt]);
+      if constexpr (J + 1 < NJ) load_pair(p + NW, pb[(J + 1) & 1]);
+      PIN_ORDER();
+      const Pair& cur = pb[J & 1];
+      f4 h2[NB][2], dact[NB][2];
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) h2[nb][tt] = dact[nb][tt] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb) {
+            h2[nb][tt] = mfma_split(cur.w1[tt][s], as[nb][s], h2[nb][tt]);
+            dact[nb][tt] = mfma_split(cur.w2t[tt][s], ds[nb][s], dact[nb][tt]);
+          }
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        f4 dh2[2];
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+          const f4 pre = h2[nb][tt] + cur.b[tt];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) dh2[tt][r] = dact[nb][tt][r] * gelu_erf_grad(pre[r]);
+          if (IO.d_h2 && W.ok[nb]) *(f4*)(IO.d_h2 + (size_t)W.row[nb] * I + 32 * p + 16 * tt + 4 * g) = dh2[tt];
+        }
+        b8 dp[3];
+        split_tiles(dh2[0], dh2[1], dp);
+#pragma unroll
+        for (int nt = 0; nt < DT; ++nt) da[nb][nt] = mfma_split(w1t[nt], dp, da[nb][nt]);
+      }
+      PIN_ORDER();
+    });
+  }
+
+  if (NW > 1) {  // fold the waves' shares of d a into wave 0
+    __shared__ f4 red[NW > 1 ? NW - 1 : 1][DT][64];
+    if (wave > 0) {
+#pragma unroll
+      for (int t = 0; t < DT; ++t) red[wave - 1][t][lane] = da[0][t];
+    }
+    __syncthreads();
+    if (wave > 0) return;
+#pragma unroll
+    for (int w = 0; w < NW - 1; ++w)
+#pragma unroll
+      for (int t = 0; t < DT; ++t) da[0][t] += red[w][t][lane];
+  }
+
+  // ---- through the first LayerNorm: d h1, d x; then d ctx = d h1 . Wd ---------------------------------------------
+  f4 dh1[NB][DT];
+  {
+    f4 acc_g[DT], acc_b[DT];
+#pragma unroll
+    for (int t = 0; t < DT; ++t) acc_g[t] = acc_b[t] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+      f4 z[DT], res[DT], keep[DT], dz[DT];
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        const size_t o = (size_t)W.row[nb] * H + 16 * t + 4 * g;
+        z[t] = *(const f4*)(S.h1 + o);
+        res[t] = *(const f4*)(P.x + (size_t)W.src[nb] * H + 16 * t + 4 * g);
+        keep[t] = row_keep_scale(P.p1, P.keep1, P.seed1 + step, W.row[nb], 4 * t + g, H);
+      }
+      const float2 st = *(const float2*)(S.st1 + 2 * (size_t)W.row[nb]);
+      ln_backward<DT>(z, res, keep, P.g1, st.x, st.y, da[nb], W.ok[nb], g, dz, acc_g, acc_b);
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        const size_t o = (size_t)W.row[nb] * H + 16 * t + 4 * g;
+        dh1[nb][t] = dz[t] * keep[t];
+        if (W.ok[nb]) {
+          if (IO.d_x) store_grad(IO.d_x + (size_t)W.src[nb] * H + 16 * t + 4 * g, dz[t], P.src_index != nullptr);
+          if (IO.d_h1) *(f4*)(IO.d_h1 + o) = dh1[nb][t];
+        }
+      }
+    }
+    if (part) {
+      store_partial<DT>(part, acc_g, c, g);
+      store_partial<DT>(part + H, acc_b, c, g);
+    }
+  }
+  if (IO.d_ctx) {
+    f4 dc[NB][DT];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int nt = 0; nt < DT; ++nt) dc[nb][nt] = f4{0.f, 0.f, 0.f, 0.f};
+    b8 hs[NB][2][3];
+    split_rows64<NB>(dh1, hs);
+    split_square<NB>(planes + L::BWD_D, lane, hs, dc);  // A[k = 16 nt + c][n] = Wd[n][k]
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+      if (W.ok[nb])
+#pragma unroll
+        for (int nt = 0; nt < DT; ++nt) store_grad(IO.d_ctx + (size_t)W.src[nb] * H + 16 * nt + 4 * g, dc[nb][nt], P.src_index != nullptr);
+  }
+}
 
 // =====================================================================================================================
 // Hidden 128 / 256 (BASELINE configs[3], [4]) [round 3].  The kernels above keep the dense weights ([H, H] as MFMA
@@ -1581,15 +2015,38 @@ int launch_wide_bwd(const acattn_tail_problem& p, const acattn_tail_saved& s, co
   return (int)hipGetLastError();
 }
 
+// hidden 64 on split products: every form but the staged one, unless ACATTN_TAIL_PRODUCTS=fp32 (measurement hook: the tails
+// alone) or acattn_linear_products(0) (the layer's linear products) asks for the exact-fp32 kernels
+bool tail_split_products(int H, int I, int rows) {
+  static const char* e = getenv("ACATTN_TAIL_PRODUCTS");
+  static const bool fp32 = e && !strcmp(e, "fp32");
+  return H == 64 && (I == 256 || I == 128) && !fp32 && acattn_linear_products_choice(-1) == 1 && !staged64(rows);
+}
+
+template <int I>
+int launch_split_planes(const acattn_tail_problem& p, void* planes, hipStream_t stream) {
+  hipLaunchKernelGGL(tail_split_planes_kernel<I>, dim3(I / 32, 6), dim3(256), 0, stream, p.wd, p.w1, p.w2, (b8*)planes);
+  return (int)hipGetLastError();
+}
+
 template <int H, int I>
 int launch_fwd(const acattn_tail_problem& p, const acattn_tail_saved& s, hipStream_t stream) {
-  if (staged64(p.rows)) {
+  if (staged64(p.rows)) {  // (split planes, if any, are not read)
     const int wgs = (p.rows + 16 * NWV - 1) / (16 * NWV);
     hipLaunchKernelGGL((tail_chunked_fwd_kernel<H, I>), dim3(wgs), dim3(64 * NWV), 0, stream, p, s);
     return (int)hipGetLastError();
   }
   const int nb = rows_per_wave(p.rows) / 16;
   const int blocks = (p.rows + 16 * nb - 1) / (16 * nb);
+  if (p.split_planes) {  // the same row blocks on split bf16 products
+    if (nb == 1 && split_slabs(p.rows))
+      hipLaunchKernelGGL((tail_split_fwd_kernel<H, I, 1, 4>), dim3(blocks), dim3(256), 0, stream, p, s);
+    else if (nb == 2)
+      hipLaunchKernelGGL((tail_split_fwd_kernel<H, I, 2>), dim3(blocks), dim3(64), 0, stream, p, s);
+    else
+      hipLaunchKernelGGL((tail_split_fwd_kernel<H, I, 1>), dim3(blocks), dim3(64), 0, stream, p, s);
+    return (int)hipGetLastError();
+  }
   if (nb == 1 && split_slabs(p.rows)) {
     hipLaunchKernelGGL((tail_fwd_kernel<H, I, 1, 4>), dim3(blocks), dim3(256), 0, stream, p, s);
     return (int)hipGetLastError();
@@ -1619,6 +2076,14 @@ int launch_bwd(const acattn_tail_problem& p, const acattn_tail_saved& s, const a
   }
   const int nb = rows_per_wave(p.rows) / 16;
   const int blocks = acattn_tail_bwd_partial_rows(p.rows);
+  // (the four-wave form of the backward stays on fp32: its split kernel measured 16.0 against 15.4 us at 512 rows)
+  if (p.split_planes && !(nb == 1 && split_slabs(p.rows))) {
+    if (nb == 2)
+      hipLaunchKernelGGL((tail_split_bwd_kernel<H, I, 2>), dim3(blocks), dim3(64), 0, stream, p, s, io);
+    else
+      hipLaunchKernelGGL((tail_split_bwd_kernel<H, I, 1>), dim3(blocks), dim3(64), 0, stream, p, s, io);
+    return (int)hipGetLastError();
+  }
   if (nb == 1 && split_slabs(p.rows)) {
     hipLaunchKernelGGL((tail_bwd_kernel<H, I, 1, 4>), dim3(blocks), dim3(256), 0, stream, p, s, io);
     return (int)hipGetLastError();
@@ -1642,6 +2107,18 @@ int acattn_tail_bwd_partial_rows_h(int rows, int H) {
 }
 // (hidden 64 needs it for the staged form only, i.e. above the slab-split row count; asking for it always is simpler)
 int64_t acattn_tail_bwd_ws_bytes(int H, int I) { return ((int64_t)2 * H * I + (int64_t)H * H) * (int64_t)sizeof(float); }
+
+int64_t acattn_tail_split_bytes(int H, int I, int rows) {
+  if (!tail_split_products(H, I, rows)) return 0;
+  return (int64_t)(I == 256 ? TailPlanes<256>::TOTAL : TailPlanes<128>::TOTAL) * (int64_t)sizeof(b8);
+}
+
+int acattn_launch_tail_split(const acattn_tail_problem& p, void* planes, hipStream_t stream) {
+  if (p.H == 64 && p.I == 256) return launch_split_planes<256>(p, planes, stream);
+  if (p.H == 64 && p.I == 128) return launch_split_planes<128>(p, planes, stream);
+  acattn_set_error("layer tail split planes: hidden 64, inner 256 or 128 only");
+  return -1;
+}
 
 int acattn_select_tail_nb(int nb) {
   const int prev = g_tail_nb;

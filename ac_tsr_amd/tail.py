@@ -4,7 +4,8 @@
     out = LayerNorm(dropout(dense_2(gelu(dense_1(a)))) + a)   FeedForward.forward,  layers.py:790-798
 
 `_FusedLayerTail` (hidden 64, inner 256 / 128: the shipped configuration): ONE HIP launch forward
-(acattn_layer_tail_fwd: the three products on the fp32 matrix cores with the chain held in registers, csrc/acattn_tail.hip)
+(acattn_layer_tail_fwd: the three products with the chain held in registers, csrc/acattn_tail.hip; at hidden 64 on bf16
+matrix instructions with exactly split operands, the weights split once per node by acattn_layer_tail_split_weights)
 and, backward, one launch for every input gradient and the LayerNorm partials (acattn_layer_tail_bwd) + the grouped
 weight-gradient launch pair + one reduction of the partials.
 
@@ -74,14 +75,24 @@ class _FusedLayerTail(torch.autograd.Function):
         # hidden 128: gelu'(dense_1(a)) is saved as well (the backward would spend a fourth of its matrix work rebuilding it)
         dgelu = new(rows, I) if (H > 64 and any(ctx.needs_input_grad)) else None
         p = _tail_problem(c, x, *params, eps1, eps2, p1, p2, k1, k2, seed1, seed2, seed_tensor, pick)
+        lib = _lib.load()
+        # hidden 64: the weights split into bf16 planes once for this node (forward and its backward); the planes are made
+        # from the weights of THIS call and die with the node, so an in-place update (Adam) can never leave them stale
+        planes = None
+        nbytes = int(lib.acattn_layer_tail_split_bytes(H, I, rows))
+        if nbytes > 0:
+            planes = new(nbytes // 4)
+            _lib.check(lib.acattn_layer_tail_split_weights(C.byref(p), _ptr(planes), _stream()), "layer_tail_split_weights")
+            p.split_planes = _ptr(planes)
         sv = _lib.TailSaved()
         sv.h1, sv.st1, sv.a, sv.act, sv.h3, sv.st2, sv.out = (_ptr(t) for t in (h1, st1, a, act, h3, st2, out))
         sv.gelu_grad = _ptr(dgelu)
-        _lib.check(_lib.load().acattn_layer_tail_fwd(C.byref(p), C.byref(sv), _stream()), "layer_tail_fwd")
+        _lib.check(lib.acattn_layer_tail_fwd(C.byref(p), C.byref(sv), _stream()), "layer_tail_fwd")
         empty = c.new_empty(0)
         ctx.save_for_backward(c, x, h1, st1, a, act, h3, st2, *params, k1 if k1 is not None else empty,
                               k2 if k2 is not None else empty, seed_tensor if seed_tensor is not None else empty,
-                              pick if pick is not None else empty, dgelu if dgelu is not None else empty)
+                              pick if pick is not None else empty, dgelu if dgelu is not None else empty,
+                              planes if planes is not None else empty)
         ctx.args = (eps1, eps2, p1, p2, k1 is not None, k2 is not None, seed1, seed2, seed_tensor is not None,
                     pick is not None)
         return out
@@ -90,7 +101,7 @@ class _FusedLayerTail(torch.autograd.Function):
     def backward(ctx, d_out):
         c, x, h1, st1, a, act, h3, st2 = ctx.saved_tensors[:8]
         params = ctx.saved_tensors[8:18]
-        k1, k2, seed_t, pick, dgelu = ctx.saved_tensors[18:]
+        k1, k2, seed_t, pick, dgelu, planes = ctx.saved_tensors[18:]
         eps1, eps2, p1, p2, has_k1, has_k2, seed1, seed2, has_seed_t, has_pick = ctx.args
         k1, k2, seed_t = (k1 if has_k1 else None), (k2 if has_k2 else None), (seed_t if has_seed_t else None)
         pick = pick if has_pick else None
@@ -101,6 +112,7 @@ class _FusedLayerTail(torch.autograd.Function):
         new = lambda *shape: torch.empty(*shape, device=c.device, dtype=torch.float32)
         d_out = d_out.contiguous()
         p = _tail_problem(c, x, *params, eps1, eps2, p1, p2, k1, k2, seed1, seed2, seed_t, pick)
+        p.split_planes = _ptr(planes) if planes.numel() else None  # the forward's planes: the same products both ways
         sv = _lib.TailSaved()
         sv.h1, sv.st1, sv.a, sv.act, sv.h3, sv.st2 = (_ptr(t) for t in (h1, st1, a, act, h3, st2))
         sv.gelu_grad = _ptr(dgelu) if dgelu.numel() else None

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ACATTN_ABI_VERSION 30
+#define ACATTN_ABI_VERSION 31
 
 /* attention-mask encodings (recbole/model/abstract_recommender.py:136-143 builds the dense form) */
 enum {
@@ -444,6 +444,12 @@ typedef struct acattn_tail_problem {
    * zero-fills those two.  NULL = identity. */
   const int64_t* src_index;
   int32_t src_R, src_L;
+  /* ABI 31, optional: hidden 64 only, the weight planes acattn_layer_tail_split_weights wrote from THESE wd / w1 / w2
+   * (acattn_layer_tail_split_bytes(H, I, rows) bytes, 16-byte aligned).  Given, the products run on bf16 matrix
+   * instructions with exactly split operands (per element closer to fp64 than fp32, with a small negative mean error
+   * that adds up in sums over many rows: DESIGN.md 4.7); NULL = the exact-fp32 kernels.  The
+   * planes are a copy of the weights: after any change of wd / w1 / w2 they must be written again before use. */
+  const void* split_planes;
 } acattn_tail_problem;
 
 /* Tensors the forward writes and the backward reads (all required in both directions, `act` forward only). */
@@ -484,6 +490,13 @@ int32_t acattn_layer_tail_bwd_partial_rows_for(int32_t rows, int32_t H); /* any 
 int64_t acattn_layer_tail_bwd_workspace_bytes(int32_t H, int32_t I);
 /* Measurement hook: rows per wave of the forward = 16 * nb (0 = chosen by size).  Returns the previous setting. */
 int acattn_select_layer_tail_blocks(int nb);
+/* ABI 31: bytes of the split weight planes of acattn_tail_problem.split_planes for a tail of `rows` rows, or 0 where the
+ * exact-fp32 kernels run: hidden other than 64, rows of the staged form, acattn_linear_products(ACATTN_LINEAR_PRODUCTS_FP32)
+ * or the environment variable ACATTN_TAIL_PRODUCTS=fp32 (the tails alone).  The answer may change with those settings:
+ * ask before each forward. */
+int64_t acattn_layer_tail_split_bytes(int32_t H, int32_t I, int32_t rows);
+/* ABI 31: writes the planes of p->wd, p->w1, p->w2 (hidden 64) into `planes` (one launch on `stream`). */
+int acattn_layer_tail_split_weights(const acattn_tail_problem* p, void* planes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * The six projections in front of the attention core in one launch (forward) / one launch (input gradients):
@@ -540,7 +553,8 @@ int acattn_projections_bwd(const acattn_proj_problem* p, const acattn_proj_bwd_i
 /* ABI 30: arithmetic of the hidden-64 projection products (acattn_projections_fwd / _bwd).  ACATTN_LINEAR_PRODUCTS_FP32:
  * the exact-fp32 matrix instruction; ACATTN_LINEAR_PRODUCTS_DEFAULT: bf16 matrix instructions on operands split exactly
  * into three bf16 planes (six products per pair, as accurate as fp32: DESIGN.md 4.6) wherever the gate has at most 64
- * outputs.  Hidden 128 / 256 always use fp32.  The environment variable ACATTN_LINEAR_PRODUCTS=fp32 sets the initial mode.
+ * outputs.  ABI 31: the same mode chooses the products of the hidden-64 layer tails (acattn_layer_tail_split_bytes
+ * answers 0 in mode ACATTN_LINEAR_PRODUCTS_FP32).  Hidden 128 / 256 always use fp32.  The environment variable ACATTN_LINEAR_PRODUCTS=fp32 sets the initial mode.
  * Process-wide; returns the previous mode; any other value only queries. */
 #define ACATTN_LINEAR_PRODUCTS_FP32 0
 #define ACATTN_LINEAR_PRODUCTS_DEFAULT 1
