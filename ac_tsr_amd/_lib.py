@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("ACATTN_LIB") or os.path.join(CSRC, "libacattn.so")  # ACATTN_LIB: experiments only
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "acattn.h")
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 MAX_MASKS = 8  # ACATTN_MAX_MASKS
 NSTAT = 8
 MASK_STRUCTURED, MASK_DENSE_LL, MASK_DENSE_L = 0, 1, 2
@@ -58,6 +58,14 @@ class BwdIO(C.Structure):
         ("active_qblocks", _f), ("attack_only", C.c_int32), ("workspace", _f), ("read_rows", _f),
         ("n_read_rows", C.c_int32), ("d_penalty_part", _f), ("dgate_summed", C.c_int32),
         ("d_ctx_calibrated2", _f), ("d_penalty_part2", _f), ("dqa2", _f), ("dka2", _f),
+    ]
+
+
+class SpatialBwdIO(C.Structure):
+    _fields_ = [
+        ("d_ctx", _f), ("dq", _f), ("dk", _f), ("dv", _f),
+        ("dw_order_part", _f), ("dw_dist_part", _f), ("dsmall_part", _f), ("part_stride", C.c_int32),
+        ("n_read_rows", C.c_int32), ("read_rows", _f), ("workspace", _f),
     ]
 
 
@@ -140,6 +148,8 @@ SYMBOLS = {
     "acattn_fwd_algorithmic_bytes": (C.c_int64, [C.POINTER(Problem)]),
     "acattn_calibrated_attention_fwd": (C.c_int, [C.POINTER(Problem), C.POINTER(FwdOut), C.c_void_p]),
     "acattn_calibrated_attention_bwd": (C.c_int, [C.POINTER(Problem), C.POINTER(BwdIO), C.c_void_p]),
+    "acattn_spatial_attention_bwd": (C.c_int, [C.POINTER(Problem), C.POINTER(SpatialBwdIO), C.c_void_p]),
+    "acattn_spatial_attention_bwd_workspace_bytes": (C.c_int64, [C.POINTER(Problem)]),
     "acattn_spatial_affines": (C.c_int, [C.POINTER(Problem), _f, C.c_void_p]),
     "acattn_full_sort_ce_workspace_bytes": (C.c_int64, [C.POINTER(CeProblem)]),
     "acattn_full_sort_ce_fwd": (C.c_int, [C.POINTER(CeProblem), _f, _f, _f, C.c_void_p]),
@@ -154,6 +164,8 @@ SYMBOLS = {
     "acattn_projections_supported": (C.c_int, [C.c_int32, C.c_int32]),
     "acattn_projections_bwd_workspace_bytes": (C.c_int64, [C.POINTER(ProjProblem)]),
     "acattn_projections_fwd": (C.c_int, [C.POINTER(ProjProblem), C.POINTER(ProjOut), C.c_void_p]),
+    "acattn_projections_qkv_supported": (C.c_int, [C.c_int32]),
+    "acattn_projections_qkv_fwd": (C.c_int, [C.POINTER(ProjProblem), C.POINTER(ProjOut), C.c_void_p]),
     "acattn_projections_bwd": (C.c_int, [C.POINTER(ProjProblem), C.POINTER(ProjBwdIO), C.c_void_p]),
     "acattn_layer_tail_supported": (C.c_int, [C.c_int32, C.c_int32]),
     "acattn_layer_tail_fwd": (C.c_int, [C.POINTER(TailProblem), C.POINTER(TailSaved), C.c_void_p]),

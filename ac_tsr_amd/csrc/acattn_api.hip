@@ -136,6 +136,26 @@ int64_t acattn_calibrated_attention_bwd_workspace_bytes(const acattn_problem* p)
   return acattn_bwd_stream_ws_bytes(*p);
 }
 
+int acattn_spatial_attention_bwd(const acattn_problem* p, const acattn_spatial_bwd_io* io, void* stream) {
+  if (int rc = check_problem(p)) return rc;
+  if (!io) return fail("io is NULL");
+  if (p->adversarial) return fail("the spatial-only backward needs adversarial == 0 (use acattn_calibrated_attention_bwd)");
+  if (!io->d_ctx) return fail("d_ctx must be non-NULL");
+  if (!io->dq || !io->dk || !io->dv) return fail("dq, dk, dv must be non-NULL");
+  if (!io->dw_order_part || !io->dw_dist_part || !io->dsmall_part) return fail("parameter partial buffers must be non-NULL");
+  if (io->part_stride != 0 && io->part_stride < 2 * (p->H / p->n_heads)) return fail("part_stride is smaller than a partial row");
+  if (!io->workspace) return fail("workspace must be non-NULL (acattn_spatial_attention_bwd_workspace_bytes)");
+  if (io->read_rows && io->n_read_rows < 1) return fail("read_rows given with n_read_rows < 1");
+  const int rc = acattn_launch_spatial_bwd(*p, *io, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
+int64_t acattn_spatial_attention_bwd_workspace_bytes(const acattn_problem* p) {
+  if (!p || p->B < 1 || p->L < 1 || p->n_heads < 1) return -1;
+  return acattn_spatial_bwd_ws_bytes(*p);
+}
+
 int acattn_rng_materialize(int32_t B, int32_t n_heads, int32_t L, uint64_t seed, float p_drop, float* noise,
                            uint8_t* keep_after, uint8_t* keep_mask, uint8_t* keep_before, void* stream) {
   if (B < 1 || n_heads < 1 || L < 1) return fail("B, n_heads, L must be positive");
@@ -243,6 +263,25 @@ int acattn_projections_fwd(const acattn_proj_problem* p, const acattn_proj_out* 
     if (p->L < 1 || p->rows % p->L != 0) return fail("projections: affine planes need rows = B * L");
   }
   const int rc = acattn_launch_proj_fwd(*p, *out, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
+int acattn_projections_qkv_supported(int32_t H) { return acattn_proj_qkv_supported(H) ? 1 : 0; }
+
+int acattn_projections_qkv_fwd(const acattn_proj_problem* p, const acattn_proj_out* out, void* stream) {
+  if (!p) return fail("problem must be non-NULL");
+  if (p->rows < 1) return fail("rows must be positive");
+  if (!acattn_proj_qkv_supported(p->H)) return fail("projections (q, k, v only): hidden_size must be 64 with the split products on");
+  if (!p->x || !p->wq || !p->bq || !p->wk || !p->bk || !p->wv || !p->bv) return fail("projections: input and parameters must be non-NULL");
+  if (!out || !out->mq || !out->mk || !out->mv) return fail("projections: outputs must be non-NULL");
+  if (out->qa || out->ka || out->gate) return fail("projections (q, k, v only): qa, ka and gate outputs must be NULL");
+  if (out->affine) {
+    if (!p->w_order || !p->b_order || !p->w_dist || !p->b_dist) return fail("projections: affine planes need the spatial calibrator's parameters");
+    if (p->n_heads < 1 || p->H % p->n_heads != 0 || (p->H / p->n_heads) % 16 != 0) return fail("projections: affine planes need a head size that is a multiple of 16");
+    if (p->L < 1 || p->rows % p->L != 0) return fail("projections: affine planes need rows = B * L");
+  }
+  const int rc = acattn_launch_proj_qkv_fwd(*p, *out, (hipStream_t)stream);
   if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
   return rc;
 }

@@ -324,6 +324,8 @@ int64_t acattn_bwd_stream_ws_bytes(const acattn_problem& p);
 int acattn_launch_bwd(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream);
 bool acattn_bwd_gate_summed(const acattn_problem& p, const acattn_bwd_io& io);
 bool acattn_bwd_pair_supported(const acattn_problem& p, const acattn_bwd_io& io);  // acattn_bwd_io.dqa2 (acattn_bwd.hip)  // acattn_bwd_io.dgate_summed (acattn_bwd.hip)
+int64_t acattn_spatial_bwd_ws_bytes(const acattn_problem& p);
+int acattn_launch_spatial_bwd(const acattn_problem& p, const acattn_spatial_bwd_io& io, hipStream_t stream);  // acattn_bwd_spatial.hip
 int acattn_launch_spatial_affines(const acattn_problem& p, float* affine, hipStream_t stream);
 int acattn_launch_rng(int B, int nh, int L, uint64_t seed, float p_drop, float* noise, uint8_t* keep_after,
                       uint8_t* keep_mask, uint8_t* keep_before, hipStream_t stream);
@@ -343,6 +345,8 @@ void acattn_set_error(const char* msg);
 bool acattn_proj_supported(int H, int G);
 int64_t acattn_proj_bwd_ws_bytes(const acattn_proj_problem& p);
 int acattn_launch_proj_fwd(const acattn_proj_problem& p, const acattn_proj_out& o, hipStream_t stream);
+bool acattn_proj_qkv_supported(int H);
+int acattn_launch_proj_qkv_fwd(const acattn_proj_problem& p, const acattn_proj_out& o, hipStream_t stream);
 int acattn_launch_proj_bwd(const acattn_proj_problem& p, const acattn_proj_bwd_io& io, hipStream_t stream);
 bool acattn_tail_supported(int H, int I);
 int acattn_tail_bwd_partial_rows(int rows);

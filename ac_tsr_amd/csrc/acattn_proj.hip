@@ -1129,6 +1129,44 @@ __global__ void __launch_bounds__(64 * SPW) proj_split_fwd_kernel(const acattn_p
   store_rows<4, NB>(O.mv, W, g, acc);
 }
 
+// The three projections of a layer WITHOUT the adversarial calibrator (mq, mk, mv; acattn_projections_qkv_fwd): the
+// chains of proj_split_fwd_kernel that end in an attack transform or the gate left out.  LDS matrices: Wq, Wk, Wv.
+constexpr int SPLIT_QKV_LDS = 3 * SPLIT_MAT * (int)sizeof(b8);
+template <int NB>
+__global__ void __launch_bounds__(64 * SPW) proj_split_qkv_fwd_kernel(const acattn_proj_problem P, const acattn_proj_out O) {
+  extern __shared__ b8 wsp[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
+  const Rows<NB> W = split_rows_of<NB>(P.rows, wave);
+  {
+    const float* src[3] = {P.wq, P.wk, P.wv};
+    float v[3][2][8];
+#pragma unroll
+    for (int m = 0; m < 3; ++m) split_raw<false>(src[m], 64, wave, c, g, v[m]);
+#pragma unroll
+    for (int m = 0; m < 3; ++m) split_store(v[m], wsp + m * SPLIT_MAT, wave, lane);
+  }
+  f4 xb[NB][4], acc[NB][4];
+  b8 xs[NB][2][3];
+  f4 bias[4];
+  load_rows<4, NB>(P.x, W, g, xb);
+  load_bias<4>(P.bq, g, bias);
+  __syncthreads();
+  split_rows<NB>(xb, xs);
+  set_rows<4, NB>(bias, acc);
+  split_product<NB>(wsp, lane, xs, acc);  // mq
+  store_rows<4, NB>(O.mq, W, g, acc);
+  if (O.affine) write_affine<4, NB>(acc, W, P, O.affine, 0, P.b_order[0], P.b_dist[0], 0, c, g);
+  load_bias<4>(P.bk, g, bias);
+  set_rows<4, NB>(bias, acc);
+  split_product<NB>(wsp + SPLIT_MAT, lane, xs, acc);  // mk
+  store_rows<4, NB>(O.mk, W, g, acc);
+  if (O.affine) write_affine<4, NB>(acc, W, P, O.affine, 64 / P.n_heads, 0.f, 0.f, 2, c, g);
+  load_bias<4>(P.bv, g, bias);
+  set_rows<4, NB>(bias, acc);
+  split_product<NB>(wsp + 2 * SPLIT_MAT, lane, xs, acc);  // mv
+  store_rows<4, NB>(O.mv, W, g, acc);
+}
+
 // LDS matrices of the backward (transposed): Waq, Wg, Wq, Wak, Wk, Wv.  MODE as in proj_bwd_kernel.
 template <int NB, int MODE>
 __global__ void __launch_bounds__(64 * SPW) proj_split_bwd_kernel(const acattn_proj_problem P, const acattn_proj_bwd_io IO) {
@@ -1347,6 +1385,30 @@ int acattn_launch_proj_fwd(const acattn_proj_problem& p, const acattn_proj_out& 
   else
     hipLaunchKernelGGL((proj_fwd_kernel<64, 1>), dim3(blocks), dim3(64), 0, stream, p, o);
   return (int)hipGetLastError();
+}
+
+// mq, mk, mv alone: served at hidden 64 on the split products (the form the training step runs); every other width or
+// mode is three plain linear layers for the caller.
+bool acattn_proj_qkv_supported(int H) { return H == 64 && linear_products() == 1; }
+
+namespace {
+template <int NB>
+int launch_split_qkv_fwd(const acattn_proj_problem& p, const acattn_proj_out& o, hipStream_t stream) {
+  static const bool lds_ok = hipFuncSetAttribute((const void*)proj_split_qkv_fwd_kernel<NB>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_QKV_LDS) == hipSuccess;
+  if (!lds_ok) return (int)hipErrorInvalidValue;
+  const int wgs = (p.rows + 16 * NB * SPW - 1) / (16 * NB * SPW);
+  hipLaunchKernelGGL((proj_split_qkv_fwd_kernel<NB>), dim3(wgs), dim3(64 * SPW), SPLIT_QKV_LDS, stream, p, o);
+  return (int)hipGetLastError();
+}
+}  // namespace
+
+int acattn_launch_proj_qkv_fwd(const acattn_proj_problem& p, const acattn_proj_out& o, hipStream_t stream) {
+  if (!acattn_proj_qkv_supported(p.H)) {
+    acattn_set_error("projections (q, k, v only): hidden_size must be 64 with the split products on");
+    return -1;
+  }
+  return rows_per_wave(p.rows) == 32 ? launch_split_qkv_fwd<2>(p, o, stream) : launch_split_qkv_fwd<1>(p, o, stream);
 }
 
 int acattn_launch_proj_bwd(const acattn_proj_problem& p, const acattn_proj_bwd_io& io, hipStream_t stream) {

@@ -37,6 +37,12 @@ _LIB.define(
     "float p_drop, int seed, Tensor? seed_tensor, bool gate_is_prob, Tensor attack_mask, Tensor row_stats, "
     "Tensor? d_ctx_attacked, Tensor? d_ctx_calibrated, Tensor? d_attack_mask, Tensor? read_rows, Tensor? active_qblocks, "
     "bool attack_only, Tensor? d_penalty_part=None) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)")
+# Backward of the spatial-only operator (adversarial == False of the forward above).  ONE output shape whatever the
+# arguments: (dq, dk, dv [B,L,H], parameter partials [B * n_heads, 4 * dh + 4] in the layout of acattn_bwd_io).
+_LIB.define(
+    "spatial_attention_bwd(Tensor q, Tensor k, Tensor v, Tensor key_valid, bool causal, Tensor w_order, Tensor b_order, "
+    "Tensor w_dist, Tensor b_dist, Tensor scalar, int n_heads, float p_drop, int seed, Tensor? seed_tensor, Tensor d_ctx, "
+    "Tensor? read_rows=None) -> (Tensor, Tensor, Tensor, Tensor)")
 
 
 import os
@@ -231,6 +237,29 @@ def _bwd_meta(q, k, v, qa, ka, gate, key_valid, causal, w_order, b_order, w_dist
     return e(), e(), e(), e(), e(), q.new_empty(B, 1 if one else n_heads, L, L), q.new_empty(B * n_heads, 4 * dh + 4)
 
 
+def _spatial_bwd_cuda(q, k, v, key_valid, causal, w_order, b_order, w_dist, b_dist, scalar, n_heads, p_drop, seed, seed_tensor,
+                      d_ctx, read_rows=None):
+    B, L, H, dh = _check_problem(q, k, v, None, None, None, key_valid, w_order, b_order, w_dist, b_dist, scalar, n_heads,
+                                 seed_tensor, None, False)
+    _check("d_ctx", d_ctx, (B, L, H), torch.float32, q.device)
+    if read_rows is not None:
+        if read_rows.dim() != 2 or read_rows.shape[0] != B or read_rows.shape[1] < 1:
+            raise ValueError(f"acattn: `read_rows` must be [B, n] (got {tuple(read_rows.shape)})")
+        _check("read_rows", read_rows, None, torch.int64, q.device)
+    prob = _problem(q, k, v, None, None, None, key_valid, causal, w_order, b_order, w_dist, b_dist, scalar, n_heads, p_drop,
+                    seed, seed_tensor, False, None, False)
+    from .ops import spatial_attention_bwd_launch
+    return spatial_attention_bwd_launch(_lib.load(), prob, q, d_ctx, n_heads, read_rows, poison=_POISON)
+
+
+def _spatial_bwd_meta(q, k, v, key_valid, causal, w_order, b_order, w_dist, b_dist, scalar, n_heads, p_drop, seed, seed_tensor,
+                      d_ctx, read_rows=None):
+    B, L, H = q.shape
+    return torch.empty_like(q), torch.empty_like(q), torch.empty_like(q), q.new_empty(B * n_heads, 4 * (H // n_heads) + 4)
+
+
+_LIB.impl("spatial_attention_bwd", _spatial_bwd_cuda, "CUDA")
+_LIB.impl("spatial_attention_bwd", _spatial_bwd_meta, "Meta")
 _LIB.impl("calibrated_attention_fwd", _fwd_cuda, "CUDA")
 _LIB.impl("calibrated_attention_fwd", _fwd_meta, "Meta")
 _LIB.impl("calibrated_attention_bwd", _bwd_cuda, "CUDA")
@@ -243,6 +272,11 @@ def _setup_context(ctx, inputs, output):
      gate_is_prob, affine, adversarial) = inputs[:20]
     if not adversarial:
         ctx.adversarial = False
+        ctx.args = (causal, n_heads, p_drop, seed)
+        ctx.save_for_backward(q, k, v, key_valid, w_order, b_order, w_dist, b_dist, scalar,
+                              seed_tensor if seed_tensor is not None else q.new_empty(0))
+        ctx.has_seed_tensor = seed_tensor is not None
+        ctx.set_materialize_grads(False)
         return
     ctx.adversarial = True
     ctx.args = (causal, n_heads, p_drop, seed, gate_is_prob)
@@ -252,9 +286,25 @@ def _setup_context(ctx, inputs, output):
     ctx.set_materialize_grads(False)
 
 
+def _spatial_backward(ctx, d_cal):
+    if d_cal is None:
+        return (None,) * 21
+    q, k, v, key_valid, w_order, b_order, w_dist, b_dist, scalar, seed_t = ctx.saved_tensors
+    causal, n_heads, p_drop, seed = ctx.args
+    dq, dk, dv, part = torch.ops.acattn.spatial_attention_bwd(
+        q, k, v, key_valid, causal, w_order, b_order, w_dist, b_dist, scalar, n_heads, p_drop, seed,
+        seed_t if ctx.has_seed_tensor else None, d_cal.contiguous(), None)
+    dh = q.shape[-1] // n_heads
+    tot = part.sum(0)
+    small = tot[4 * dh:]
+    return (dq, dk, dv, None, None, None, None, None, tot[:2 * dh].view_as(w_order), small[0:1].view_as(b_order),
+            tot[2 * dh:4 * dh].view_as(w_dist), small[1:2].view_as(b_dist), small[2:3].view_as(scalar), None, None, None, None,
+            None, None, None, None)
+
+
 def _backward(ctx, d_att, d_cal, d_M, _d_stats, d_pen=None):
     if not ctx.adversarial:
-        raise _lib.AcattnError("backward of the spatial-only operator is not provided")
+        return _spatial_backward(ctx, d_cal)
     q, k, v, qa, ka, gate, key_valid, w_order, b_order, w_dist, b_dist, scalar, seed_t, M, stats = ctx.saved_tensors
     causal, n_heads, p_drop, seed, gate_is_prob = ctx.args
     con = lambda t: None if t is None else t.contiguous()

@@ -23,7 +23,7 @@ import torch.nn.functional as F
 
 from . import fused_ln, ops
 from . import tail
-from .linear import projections, skinny_linear
+from .linear import projections, projections_qkv, skinny_linear
 from .ops import AttentionConfig, ExplicitRandomness, StructuredMask
 from .state import state_of
 
@@ -140,8 +140,13 @@ class AttackRTransformerLayer(nn.Module):
 
     def __init__(self, n_heads, hidden_size, intermediate_size, hidden_dropout_prob, attn_dropout_prob, hidden_act,
                  layer_norm_eps, combine_option='fixed', use_order=True, use_distance=True, two_level=True,
-                 rich_calibrated_combine='fixed', seq_length=50):
+                 rich_calibrated_combine='fixed', seq_length=50, adversarial=True):
+        """`adversarial=False` (not a reference argument; after the reference's own): the spatial calibrator alone --
+        ctx = dropout(softmax((QK^T + e_order + e_distance) / sqrt(dh) + mask)) . V (layers.py:695-740, 677-680), the
+        paper's ablation.  The attack transforms and the gate are still created (state-dict keys do not depend on the
+        switch) but are never evaluated and receive no gradient."""
         super().__init__()
+        self.adversarial = bool(adversarial)
         self.hidden_size = hidden_size
         self.attack_attention = AttackRMultiHeadAttention(
             n_heads, hidden_size, hidden_dropout_prob, attn_dropout_prob, layer_norm_eps,
@@ -164,7 +169,7 @@ class AttackRTransformerLayer(nn.Module):
             self.anneal_step += 1
         return AttentionConfig(n_heads=self.attack_attention.num_attention_heads, combine_option=self.combine_option,
                                two_level=self.two_level, rich_calibrated_combine=self.rich_calibrated_combine,
-                               adversarial=True, anneal_rate=rate)
+                               adversarial=self.adversarial, anneal_rate=rate)
 
     def forward(self, hidden_states, attention_mask, return_attention_prob=False, return_all_attention_prob=False,
                 _rnd=None, _need_attacked=True, _attack_upstream=True, _rows=None):
@@ -175,6 +180,9 @@ class AttackRTransformerLayer(nn.Module):
         last layer, abstract_recommender.py:130-134; AcBERT4Rec the masked positions, acbert4rec.py:219-225)."""
         att = self.attack_attention
         cal = att.calibrator_params()
+        if not self.adversarial:
+            return self._forward_spatial_only(hidden_states, attention_mask, return_attention_prob, return_all_attention_prob,
+                                              _rnd, _rows)
         mq, mk, mv, qa, ka, gate_logits, hidden_res, extras = projections(
             hidden_states, att.query, att.key, att.value, att.attack_query_transform, att.attack_key_transform,
             self.gate if self.combine_option == 'gate' else None, attack_upstream=_attack_upstream,
@@ -233,6 +241,41 @@ class AttackRTransformerLayer(nn.Module):
                     all_attention_prob)
         return attacked_feedforward_output, calibrated_feedforward_output, attack_mask, combined_attention_prob
 
+    def _forward_spatial_only(self, hidden_states, attention_mask, return_attention_prob, return_all_attention_prob, _rnd, _rows):
+        """The layer without the adversarial calibrator: three projections, the spatial-only attention core, ONE tail.
+        Returns (None, calibrated_feedforward_output, None, None)."""
+        if return_attention_prob or return_all_attention_prob:
+            raise ValueError("adversarial=False: the spatial-only attention core has no probability dumps "
+                             "(return_attention_prob / return_all_attention_prob need the adversarial calibrator)")
+        att = self.attack_attention
+        cal = att.calibrator_params()
+        mq, mk, mv, hidden_res, extras = projections_qkv(
+            hidden_states, att.query, att.key, att.value,
+            spatial=(cal.get("w_order"), cal.get("b_order"), cal.get("w_dist"), cal.get("b_dist"), att.num_attention_heads))
+        cfg = self._config()
+        core_rnd = None
+        if _rnd is not None:
+            core_rnd = ExplicitRandomness(keep_after=getattr(_rnd, "keep_after", None))
+        p_drop = att.attn_dropout_prob if (self.training or (core_rnd is not None and core_rnd.keep_after is not None)) else 0.0
+        _, ctx_cal, _, _ = ops.calibrated_attention(
+            mq, mk, mv, None, None, None, attention_mask, cfg, p_drop=p_drop, rnd=core_rnd,
+            seed_tensor=state_of(self).seed_tensor if core_rnd is None else None, read_rows=_rows, attack_upstream=False,
+            state=state_of(self), **extras, **cal)
+        keep_out, keep_ffn = getattr(_rnd, "keep_out_cal", None), getattr(_rnd, "keep_ffn_cal", None)
+        can_tail = ctx_cal.is_cuda and tail.supported(att, self.feed_forward)
+        one_launch = can_tail and tail.fused_supported(att, self.feed_forward)
+        if _rows is not None:
+            index = _rows.unsqueeze(-1).expand(-1, -1, hidden_states.shape[-1])
+            pick = lambda t: None if t is None else t.gather(1, index)
+            if one_launch:  # the fused tail picks the rows itself
+                out = tail.layer_tail(ctx_cal, hidden_res, att, self.feed_forward, pick(keep_out), pick(keep_ffn), pick=_rows)
+                return None, out, None, None
+            ctx_cal, hidden_res, keep_out, keep_ffn = pick(ctx_cal), pick(hidden_res), pick(keep_out), pick(keep_ffn)
+        if one_launch or (can_tail and torch.is_grad_enabled()):
+            out = tail.layer_tail(ctx_cal, hidden_res, att, self.feed_forward, keep_out, keep_ffn)
+        else:
+            out = self.feed_forward(att.output(ctx_cal, hidden_res, keep_out), keep_ffn)
+        return None, out, None, None
 
 
 class AttackRTransformerEncoder(nn.Module):
@@ -240,12 +283,15 @@ class AttackRTransformerEncoder(nn.Module):
 
     def __init__(self, n_layers=2, n_heads=2, hidden_size=64, inner_size=256, hidden_dropout_prob=0.5,
                  attn_dropout_prob=0.5, hidden_act='gelu', layer_norm_eps=1e-12, combine_option='fixed', use_order=True,
-                 use_distance=True, two_level=True, rich_calibrated_combine='fixed', seq_length=50):
+                 use_distance=True, two_level=True, rich_calibrated_combine='fixed', seq_length=50, adversarial=True):
+        """`adversarial=False`: every layer runs the spatial calibrator alone (see AttackRTransformerLayer); the attacked
+        slot of every output pair and every entry of `all_attack_masks` are then None."""
         super().__init__()
+        self.adversarial = bool(adversarial)
         layer = AttackRTransformerLayer(
             n_heads, hidden_size, inner_size, hidden_dropout_prob, attn_dropout_prob, hidden_act, layer_norm_eps,
             combine_option, use_order=use_order, use_distance=use_distance, two_level=two_level,
-            rich_calibrated_combine=rich_calibrated_combine, seq_length=seq_length)
+            rich_calibrated_combine=rich_calibrated_combine, seq_length=seq_length, adversarial=adversarial)
         self.layer = nn.ModuleList([copy.deepcopy(layer) for _ in range(n_layers)])
 
     def forward(self, hidden_states, attention_mask, output_all_encoded_layers=True, return_attention_prob=False,

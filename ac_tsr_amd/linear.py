@@ -304,6 +304,95 @@ def projections(x, query, key, value, attack_query, attack_key, gate=None, attac
     return (*out, x, {})
 
 
+class _FusedQKV(torch.autograd.Function):
+    """mq, mk, mv = query/key/value(x) (recbole/model/layers.py:687-689) as ONE HIP launch each way at hidden 64
+    (acattn_projections_qkv_fwd; acattn_projections_bwd with no attack / gate cotangents): what a layer WITHOUT the
+    adversarial calibrator needs of `_FusedProjections` -- no attack transform and no gate is evaluated.  Same split
+    bf16 products, same affine planes for the attention core, same residual hand-over (see _FusedProjections)."""
+
+    @staticmethod
+    def forward(ctx, x, wq, bq, wk, bk, wv, bv, state, spatial=None):
+        import ctypes as C
+        from . import _lib
+        from .ops import _ptr, _stream
+        x = x.contiguous()
+        params = [t.contiguous() for t in (wq, bq, wk, bk, wv, bv)]
+        p = _lib.ProjProblem()
+        p.rows, p.H, p.G, p.x = x.numel() // x.shape[-1], x.shape[-1], 0, _ptr(x)
+        p.wq, p.bq, p.wk, p.bk, p.wv, p.bv = (_ptr(t) for t in params)
+        mq, mk, mv = (torch.empty_like(x) for _ in range(3))
+        out = _lib.ProjOut()
+        out.mq, out.mk, out.mv = _ptr(mq), _ptr(mk), _ptr(mv)
+        affine = None
+        keep = []
+        if spatial is not None and x.dim() == 3:
+            w_order, b_order, w_dist, b_dist, n_heads = spatial
+            B, L, H = x.shape
+            affine = _affine_workspace(state, x.device, B, n_heads, L)
+            keep = [t.detach().reshape(-1).contiguous() for t in (w_order, b_order, w_dist, b_dist)]
+            p.w_order, p.b_order, p.w_dist, p.b_dist = (_ptr(t) for t in keep)
+            p.n_heads, p.L = n_heads, L
+            out.affine = _ptr(affine)
+        _lib.check(_lib.load().acattn_projections_qkv_fwd(C.byref(p), C.byref(out), _stream()), "projections_qkv_fwd")
+        ctx.save_for_backward(x, *params)
+        ctx.state = state
+        ctx.set_materialize_grads(False)
+        if affine is not None:
+            ctx.mark_non_differentiable(affine)
+        return mq, mk, mv, x.view_as(x), affine
+
+    @staticmethod
+    def backward(ctx, dmq, dmk, dmv, d_res=None, _d_affine=None):
+        import ctypes as C
+        from . import _lib
+        from .ops import _ptr, _stream, linear_wgrad_grouped
+        x, wq, bq, wk, bk, wv, bv = ctx.saved_tensors
+        two = lambda t: None if t is None else t.reshape(-1, t.shape[-1])
+        con = lambda t: None if t is None else t.contiguous()
+        dmq, dmk, dmv, d_res = (con(t) for t in (dmq, dmk, dmv, d_res))
+        if ctx.state.attack_pass_only:  # nothing here belongs to an attack transform, and nothing upstream does either
+            return (None,) * 9
+        dx = None
+        if ctx.needs_input_grad[0]:
+            if all(t is None for t in (dmq, dmk, dmv)):
+                dx = d_res
+            else:
+                p = _lib.ProjProblem()
+                p.rows, p.H, p.G, p.x = x.numel() // x.shape[-1], x.shape[-1], 0, _ptr(x)
+                p.wq, p.bq, p.wk, p.bk, p.wv, p.bv = (_ptr(t) for t in (wq, bq, wk, bk, wv, bv))
+                # (the library's argument check wants the attack transforms' parameters present; with no attack
+                # cotangent the kernel never reads them)
+                p.waq, p.baq, p.wak, p.bak = p.wq, p.bq, p.wk, p.bk
+                io = _lib.ProjBwdIO()
+                io.dmq, io.dmk, io.dmv, io.dx_init = _ptr(dmq), _ptr(dmk), _ptr(dmv), _ptr(d_res)
+                dx = torch.empty_like(x)
+                io.dx = _ptr(dx)
+                _lib.check(_lib.load().acattn_projections_bwd(C.byref(p), C.byref(io), _stream()), "projections_bwd (qkv)")
+        grads = [None] * 6
+        jobs = [(slot, two(x), two(g), ctx.needs_input_grad[slot + 1]) for slot, g in ((1, dmq), (3, dmk), (5, dmv))
+                if g is not None and (ctx.needs_input_grad[slot] or ctx.needs_input_grad[slot + 1])]
+        if jobs:
+            for (slot, _, _, _), (gw, gb) in zip(jobs, linear_wgrad_grouped([(i, g, wb) for _, i, g, wb in jobs], ctx.state)):
+                grads[slot - 1], grads[slot] = gw, gb
+        return (dx, *grads, None, None)
+
+
+def projections_qkv(x, query, key, value, spatial=None):
+    """(mq, mk, mv, x_res, extras) of an encoder layer WITHOUT the adversarial calibrator: the three projections the
+    spatial-only attention core consumes and nothing else.  One launch at hidden 64 on the split bf16 products
+    (`_FusedQKV`); three `skinny_linear` calls wherever that launch does not apply (other widths, exact-fp32 mode, CPU).
+    `x_res`, `extras`, `spatial` as in `projections`."""
+    if x.is_cuda and FUSED_PROJECTIONS and x.dtype == torch.float32 and all(m.bias is not None for m in (query, key, value)):
+        from . import _lib
+        if _lib.load().acattn_projections_qkv_supported(x.shape[-1]):
+            if not PRODUCER_EXTRAS or (spatial is not None and any(t is None for t in spatial[:4])):
+                spatial = None
+            mq, mk, mv, x_res, affine = _FusedQKV.apply(x, query.weight, query.bias, key.weight, key.bias, value.weight,
+                                                         value.bias, state_of(query), spatial)
+            return mq, mk, mv, x_res, ({} if affine is None else {"affine": affine})
+    return skinny_linear(x, query), skinny_linear(x, key), skinny_linear(x, value), x, {}
+
+
 class _FullSortScores(torch.autograd.Function):
     """scores = output @ E^T over the whole catalogue (acsasrec.py:118-119), with the input gradient
     d_output = d_scores @ E computed as a batched split-K product: its reduction runs over all N items

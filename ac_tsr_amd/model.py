@@ -144,6 +144,10 @@ class ACSASRec(SequentialRecommender):
         # The reference never forwards seq_length (acsasrec.py:40-54), which pins the gate to L = 50
         # (layers.py:863,878).  `gate_seq_length` is an opt-in extension for other lengths.
         seq_length = _cfg(config, 'gate_seq_length', 50)
+        # not a reference key: False = the spatial calibrator alone (the paper's ablation; BASELINE configuration 2).  The
+        # attack transforms and the gate still exist (same state-dict keys) but are never evaluated or trained; forward
+        # returns None in the attacked slot, calculate_loss (None, calibrated_loss), predict (None, scores).
+        self.adversarial_calibrator = bool(_cfg(config, 'adversarial_calibrator', True))
 
         self.item_embedding = nn.Embedding(self.n_items, self.hidden_size, padding_idx=0)
         if self.use_position_embedding:
@@ -153,7 +157,8 @@ class ACSASRec(SequentialRecommender):
             hidden_dropout_prob=self.hidden_dropout_prob, attn_dropout_prob=self.attn_dropout_prob,
             hidden_act=self.hidden_act, layer_norm_eps=self.layer_norm_eps, combine_option=self.combine_option,
             use_order=self.use_order, use_distance=self.use_distance, two_level=self.two_level,
-            rich_calibrated_combine=self.rich_calibrated_combine, seq_length=seq_length)
+            rich_calibrated_combine=self.rich_calibrated_combine, seq_length=seq_length,
+            adversarial=self.adversarial_calibrator)
         self.LayerNorm = nn.LayerNorm(self.hidden_size, eps=self.layer_norm_eps)
         self.dropout = nn.Dropout(self.hidden_dropout_prob)
         if self.trainable_mask_loss_weight:
@@ -189,13 +194,13 @@ class ACSASRec(SequentialRecommender):
         if not self.step_state.prune_dead_work:  # the reference's full schedule (acsasrec.py:99-103)
             trm_output = self.trm_encoder(input_emb, mask, output_all_encoded_layers=True, _rnds=_rnds)
             attacked_output, calibrated_output = trm_output[0][-1]
-            return (self.gather_indexes(attacked_output, item_seq_len - 1),
+            return (None if attacked_output is None else self.gather_indexes(attacked_output, item_seq_len - 1),
                     self.gather_indexes(calibrated_output, item_seq_len - 1), trm_output[1])
         last = (item_seq_len - 1).view(-1, 1) if _last_row is None else _last_row.view(-1, 1)
         trm_output = self.trm_encoder(input_emb, mask, output_all_encoded_layers=False, _rnds=_rnds, _last_rows=last)
         all_attack_masks = trm_output[1]
         attacked_output, calibrated_output = trm_output[0][-1]
-        return attacked_output.squeeze(1), calibrated_output.squeeze(1), all_attack_masks
+        return (None if attacked_output is None else attacked_output.squeeze(1)), calibrated_output.squeeze(1), all_attack_masks
 
     def _cal_loss(self, output, interaction, attack_loss=False):
         pos_items = interaction[self.POS_ITEM_ID]
@@ -244,7 +249,7 @@ class ACSASRec(SequentialRecommender):
         test_item = interaction[self.ITEM_ID]
         attacked_output, calibrated_output, _ = self.forward(item_seq, item_seq_len)
         test_item_emb = self.item_embedding(test_item)
-        attacked_scores = torch.mul(attacked_output, test_item_emb).sum(dim=1)
+        attacked_scores = None if attacked_output is None else torch.mul(attacked_output, test_item_emb).sum(dim=1)
         scores = torch.mul(calibrated_output, test_item_emb).sum(dim=1)
         return attacked_scores, scores
 
@@ -294,6 +299,9 @@ class AcBERT4Rec(SequentialRecommender):
         self.dp_mask_penalty = _cfg(config, 'dp_mask_penalty') or 'local'
         assert self.dp_mask_penalty in ('local', 'global'), self.dp_mask_penalty
         self.cloze_on_device = bool(_cfg(config, 'cloze_on_device', False))
+        if not _cfg(config, 'adversarial_calibrator', True):
+            raise NotImplementedError("AcBERT4Rec: adversarial_calibrator=False (the spatial calibrator alone) is provided "
+                                      "for ACSASRec only")
         seq_length = _cfg(config, 'gate_seq_length', 50)
 
         self.mask_token = self.n_items

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 from dataclasses import dataclass
 from typing import Optional
 
@@ -19,7 +20,7 @@ import torch
 
 from . import _lib
 from .state import DEFAULT as _DEFAULT_STATE
-from ._lib import BwdIO, FwdOut, Problem
+from ._lib import BwdIO, FwdOut, Problem, SpatialBwdIO
 
 
 @dataclass
@@ -271,7 +272,7 @@ class _CalibratedAttention(torch.autograd.Function):
         (q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar, rich_ratio, M, stats) = ctx.saved_tensors
         cfg = ctx.cfg
         if not cfg.adversarial:
-            raise _lib.AcattnError("backward of the spatial-only operator is not provided")
+            return _CalibratedAttention._spatial_backward(ctx, d_cal)
         lib = _lib.load()
         B, L, H = q.shape
         nh, dh = cfg.n_heads, H // cfg.n_heads
@@ -325,6 +326,44 @@ class _CalibratedAttention(torch.autograd.Function):
         _lib.check(lib.acattn_calibrated_attention_bwd(C.byref(prob), C.byref(io), _stream()), "calibrated_attention_bwd")
         return _CalibratedAttention._finish_backward(lib, attack_only, dq, dk, dv, dqa, dka, dgate_part, part, dh, w_order,
                                                      b_order, w_dist, b_dist, scalar, rich_ratio, ctx.state)
+
+    @staticmethod
+    def _spatial_backward(ctx, d_cal):
+        """Backward of the spatial-only operator (acattn_spatial_attention_bwd): dq, dk, dv and the calibrator gradients;
+        nothing is saved by that forward, the kernels rebuild the probabilities from the inputs and the dropout key.
+        Like `backward` it mutates no saved state (the trainer may walk a node twice)."""
+        (q, k, v, _qa, _ka, _gate, w_order, b_order, w_dist, b_dist, scalar, _rr, _M, _stats) = ctx.saved_tensors
+        if d_cal is None:
+            return (None,) * 24
+        cfg = ctx.cfg
+        lib = _lib.load()
+        B, L, H = q.shape
+        nh, dh = cfg.n_heads, H // cfg.n_heads
+        d_cal = d_cal.contiguous()
+        read_rows = ctx.read_rows  # (more than four read positions are kept as a block bitmap, the adversarial kernels' form:
+        #                            every block runs then, which the promise allows)
+        if ctx.via_dispatcher:
+            dq, dk, dv, part = torch.ops.acattn.spatial_attention_bwd(
+                q, k, v, ctx.mask.key_valid, bool(ctx.mask.causal), w_order.reshape(-1).contiguous(), b_order,
+                w_dist.reshape(-1).contiguous(), b_dist, scalar, nh, float(ctx.p_drop), int(ctx.seed) & 0x7FFFFFFFFFFFFFFF,
+                ctx.seed_tensor, d_cal, read_rows)
+        else:
+            keep = []
+            wo = w_order.reshape(-1) if w_order is not None else None
+            wd = w_dist.reshape(-1) if w_dist is not None else None
+            prob = _fill_problem(q, k, v, None, None, None, ctx.mask, wo, b_order, wd, b_dist, scalar, None, cfg, ctx.p_drop,
+                                 ctx.rnd, ctx.seed, keep, ctx.seed_tensor)
+            dq, dk, dv, part = spatial_attention_bwd_launch(lib, prob, q, d_cal, nh, read_rows)
+        tot = sum_rows0(part, ctx.state)
+        small = tot[4 * dh:]
+        g_wo = tot[:2 * dh].view_as(w_order) if w_order is not None else None
+        g_bo = small[0:1].view_as(b_order) if w_order is not None else None
+        g_wd = tot[2 * dh:4 * dh].view_as(w_dist) if w_dist is not None else None
+        g_bd = small[1:2].view_as(b_dist) if w_dist is not None else None
+        g_sc = small[2:3].view_as(scalar) if w_dist is not None else None
+        if ctx.state is not None:
+            ctx.state.watch(tot, g_wo, g_bo, g_wd, g_bd, g_sc, None)
+        return (dq, dk, dv, None, None, None, g_wo, g_bo, g_wd, g_bd, g_sc) + (None,) * 13
 
     @staticmethod
     def backward_pair(ctx, g_cal, g_att):
@@ -449,6 +488,33 @@ def calibrated_attention(q, k, v, qa, ka, gate_logits, mask, cfg: AttentionConfi
     if outs[7] is not None:
         outs[2]._acattn_pen = outs[7]  # see PENALTY_ROWS
     return outs[0], outs[1], outs[2], probs
+
+
+def spatial_attention_bwd_launch(lib, prob: Problem, q, d_ctx, n_heads: int, read_rows=None, poison: bool = False):
+    """One acattn_spatial_attention_bwd call for a filled `prob` (adversarial == 0): allocates the outputs, the
+    [B * n_heads, 4 * dh + 4] parameter-partial buffer (layout of acattn_bwd_io) and the workspace.  Returns
+    (dq, dk, dv, part).  `poison`: outputs start as NaN (ACATTN_POISON_OUTPUTS, dispatch.py)."""
+    B, L, H = q.shape
+    dh = H // n_heads
+    poison = poison or os.environ.get("ACATTN_POISON_OUTPUTS") == "1"  # (the direct C-ABI form honours it as well)
+    new = (lambda *shape: torch.full(shape, float("nan"), device=q.device, dtype=torch.float32)) if poison else \
+        (lambda *shape: torch.empty(*shape, device=q.device, dtype=torch.float32))
+    io = SpatialBwdIO()
+    io.d_ctx = _ptr(d_ctx)
+    dq, dk, dv = new(B, L, H), new(B, L, H), new(B, L, H)
+    io.dq, io.dk, io.dv = _ptr(dq), _ptr(dk), _ptr(dv)
+    width = 4 * dh + 4
+    part = new(B * n_heads, width)
+    base = part.data_ptr()
+    io.dw_order_part, io.dw_dist_part, io.dsmall_part = base, base + 4 * 2 * dh, base + 4 * 4 * dh
+    io.part_stride = width
+    if read_rows is not None:
+        io.read_rows, io.n_read_rows = _ptr(read_rows), read_rows.shape[1]
+    ws_bytes = int(lib.acattn_spatial_attention_bwd_workspace_bytes(C.byref(prob)))
+    ws = torch.empty(max(ws_bytes, 4) // 4, device=q.device, dtype=torch.float32)
+    io.workspace = _ptr(ws)
+    _lib.check(lib.acattn_spatial_attention_bwd(C.byref(prob), C.byref(io), _stream()), "spatial_attention_bwd")
+    return dq, dk, dv, part
 
 
 def materialize_randomness(B: int, n_heads: int, L: int, seed: int, p_drop: float, device) -> ExplicitRandomness:

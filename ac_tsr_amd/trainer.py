@@ -38,6 +38,10 @@ class AttackSASRecTrainer:
             except KeyError:
                 combined_backward = False
         self.combined_backward = bool(combined_backward)
+        if self.combined_backward and not getattr(model, 'adversarial_calibrator', True):
+            raise ValueError("combined_backward=True shares one walk between the attacked and the calibrated loss; a model "
+                             "with adversarial_calibrator=False has no attacked loss: use the default two-pass step "
+                             "(its second pass is then empty)")
         if self.combined_backward:
             from .combined import instrument_package
             instrument_package()  # before any forward whose graph will be walked

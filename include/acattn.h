@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ACATTN_ABI_VERSION 31
+#define ACATTN_ABI_VERSION 32
 
 /* attention-mask encodings (recbole/model/abstract_recommender.py:136-143 builds the dense form) */
 enum {
@@ -549,6 +549,13 @@ int acattn_projections_supported(int32_t H, int32_t G);
 int64_t acattn_projections_bwd_workspace_bytes(const acattn_proj_problem* p);
 int acattn_projections_fwd(const acattn_proj_problem* p, const acattn_proj_out* out, void* stream);
 int acattn_projections_bwd(const acattn_proj_problem* p, const acattn_proj_bwd_io* io, void* stream);
+/* [ABI 32] mq, mk, mv alone -- what a layer WITHOUT the adversarial calibrator needs: no attack transform and no gate is
+ * evaluated.  Reads x, wq / bq, wk / bk, wv / bv (and, for out->affine, the spatial fields) of *p; writes out->mq, mk, mv
+ * (and affine); out->qa, ka, gate must be NULL.  Served where acattn_projections_qkv_supported(H) answers 1: hidden 64 on
+ * the split bf16 products (acattn_linear_products: the answer may change with that setting).  The input gradient is
+ * acattn_projections_bwd with dqa = dka = dgate = NULL. */
+int acattn_projections_qkv_supported(int32_t H);
+int acattn_projections_qkv_fwd(const acattn_proj_problem* p, const acattn_proj_out* out, void* stream);
 
 /* ABI 30: arithmetic of the hidden-64 projection products (acattn_projections_fwd / _bwd).  ACATTN_LINEAR_PRODUCTS_FP32:
  * the exact-fp32 matrix instruction; ACATTN_LINEAR_PRODUCTS_DEFAULT: bf16 matrix instructions on operands split exactly
@@ -618,6 +625,34 @@ int acattn_calibrated_attention_bwd(const acattn_problem* p, const acattn_bwd_io
 
 /* Bytes of `acattn_bwd_io.workspace` for this problem (5 row scalars of the chained soft-max backward per query row). */
 int64_t acattn_calibrated_attention_bwd_workspace_bytes(const acattn_problem* p);
+
+/* [ABI 32] Backward of the SPATIAL-ONLY operator (acattn_problem.adversarial == 0):
+ *     ctx = dropout(softmax((q k^T + e_order + e_distance) / sqrt(dh) + mask)) . V     recbole/model/layers.py:695-740, 677-680
+ * The spatial-only forward saves nothing, so the backward rebuilds the probabilities from the forward's acattn_problem
+ * (q, k, v, the mask in any of the three modes, either or both spatial terms, p_drop and the same randomness: the counter
+ * seed / seed_device, or the explicit keep_after) and forms the row normalisers itself (csrc/acattn_bwd_spatial.hip: a row
+ * kernel and a key kernel, no float atomics on dq / dk / dv).  May be called any number of times for one forward. */
+typedef struct acattn_spatial_bwd_io {
+  const float* d_ctx; /* [B,L,H] cotangent of ctx_calibrated */
+  /* gradients, caller-allocated, fully overwritten */
+  float* dq; /* [B,L,H] */
+  float* dk; /* [B,L,H] */
+  float* dv; /* [B,L,H] */
+  /* per-(b,head) partial sums of the calibrator parameters in the layout of acattn_bwd_io; the caller reduces over
+   * (B, nh).  Fully written: the columns of a disabled term (NULL weight) and the spare fourth small column are zeros. */
+  float* dw_order_part; /* [B,nh,2*dh] */
+  float* dw_dist_part;  /* [B,nh,2*dh] */
+  float* dsmall_part;   /* [B,nh,4]: d b_order, d b_dist, d scalar, 0 */
+  int32_t part_stride;  /* as acattn_bwd_io.part_stride */
+  int32_t n_read_rows;
+  const int64_t* read_rows; /* optional [B, n_read_rows], as acattn_bwd_io.read_rows: the caller promises that d_ctx is zero
+                               outside those positions; query blocks without one are skipped (their dq rows are zeros).
+                               NULL = every row may carry a cotangent. */
+  void* workspace;          /* device scratch of acattn_spatial_attention_bwd_workspace_bytes(p) bytes (contents
+                               irrelevant): four floats per (b, head, query row) */
+} acattn_spatial_bwd_io;
+int acattn_spatial_attention_bwd(const acattn_problem* p, const acattn_spatial_bwd_io* io, void* stream);
+int64_t acattn_spatial_attention_bwd_workspace_bytes(const acattn_problem* p);
 
 /* Materialise the COUNTER-mode randomness for (seed, shape) so a run can be replayed in EXPLICIT mode. */
 int acattn_rng_materialize(int32_t B, int32_t n_heads, int32_t L, uint64_t seed, float p_drop, float* noise,
