@@ -11,16 +11,15 @@ cal_origin_qkv), :883-936 (AttackRTransformerLayer.combine_attention / forward),
 from __future__ import annotations
 
 import ctypes as C
-import math
-import os
 from dataclasses import dataclass
 from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, attn_launch
+from .attn_launch import _ptr, _stream, spatial_attention_bwd_launch  # noqa: F401  (other modules import them from here)
 from .state import DEFAULT as _DEFAULT_STATE
-from ._lib import BwdIO, FwdOut, Problem, SpatialBwdIO
+from ._lib import Problem
 
 
 @dataclass
@@ -60,10 +59,6 @@ class ExplicitRandomness:
     keep_before: Optional[torch.Tensor] = None
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _need_cuda(name: str, t: torch.Tensor, dtype=torch.float32):
     if not t.is_cuda:
         raise _lib.AcattnError(
@@ -75,82 +70,61 @@ def _need_cuda(name: str, t: torch.Tensor, dtype=torch.float32):
         raise ValueError(f"{name} must be contiguous")
 
 
-def _stream() -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _fill_problem(q, k, v, qa, ka, gate_logits, mask, w_order, b_order, w_dist, b_dist, scalar, rich_ratio,
                   cfg: AttentionConfig, p_drop: float, rnd, seed: int, keepalive: list, seed_tensor=None,
                   gate_is_prob: bool = False, affine=None) -> Problem:
+    """Checks the direct path's tensors, then attn_launch.fill_problem.  uint8 copies of explicit keep masks are appended
+    to `keepalive`: the caller holds it until the launch has returned."""
     B, L, H = q.shape
-    prob = Problem()
-    prob.B, prob.L, prob.H, prob.n_heads = B, L, H, cfg.n_heads
     for name, t in (("q", q), ("k", k), ("v", v)):
         _need_cuda(name, t)
         assert t.shape == (B, L, H), f"{name} must be [B,L,H]"
-    prob.q, prob.k, prob.v = _ptr(q), _ptr(k), _ptr(v)
-    prob.adversarial = int(cfg.adversarial)
     if cfg.adversarial:
         for name, t in (("qa", qa), ("ka", ka)):
             _need_cuda(name, t)
             assert t.shape == (B, L, H)
-        prob.qa, prob.ka = _ptr(qa), _ptr(ka)
     if cfg.combine_option not in _lib.COMBINE:
         raise KeyError(cfg.combine_option)  # layers.py:894-895
-    prob.combine_option = _lib.COMBINE[cfg.combine_option]
     if cfg.adversarial and cfg.combine_option == "gate":
         _need_cuda("gate_logits", gate_logits)
         if gate_logits.shape != (B, L, L):
             # same failure as the reference's broadcast at layers.py:888 when seq_length != L
             raise RuntimeError(f"The size of tensor a ({gate_logits.shape[-1]}) must match the size of tensor b ({L})")
-        prob.gate_logits = _ptr(gate_logits)
-        prob.gate_is_prob = int(bool(gate_is_prob))
     if affine is not None:
         _need_cuda("affine", affine)
         assert affine.shape == (B, cfg.n_heads, 4, 16 * ((L + 15) // 16)), "affine must be [B, n_heads, 4, 16*ceil(L/16)]"
-        prob.affine = _ptr(affine)
-    # mask
+    kw = {}
     if isinstance(mask, StructuredMask):
-        kv = mask.key_valid
-        _need_cuda("key_valid", kv, torch.uint8)
-        assert kv.shape == (B, L)
-        prob.mask_mode, prob.causal, prob.key_valid = _lib.MASK_STRUCTURED, int(mask.causal), _ptr(kv)
+        _need_cuda("key_valid", mask.key_valid, torch.uint8)
+        assert mask.key_valid.shape == (B, L)
+        kw.update(key_valid=mask.key_valid, causal=mask.causal)
     else:
         _need_cuda("attention_mask", mask)
         if mask.shape == (B, 1, L, L):
-            prob.mask_mode = _lib.MASK_DENSE_LL
+            kw.update(mask=mask, mask_mode=_lib.MASK_DENSE_LL)
         elif mask.shape == (B, 1, 1, L):
-            prob.mask_mode = _lib.MASK_DENSE_L
+            kw.update(mask=mask, mask_mode=_lib.MASK_DENSE_L)
         else:
             raise ValueError(f"attention_mask must be [B,1,L,L] or [B,1,1,L], got {tuple(mask.shape)}")
-        prob.mask = _ptr(mask)
-    # spatial calibrator
     if w_order is not None:
         for t in (w_order, b_order):
             _need_cuda("order_affine", t)
-        prob.w_order, prob.b_order = _ptr(w_order), _ptr(b_order)
     if w_dist is not None:
         for t in (w_dist, b_dist, scalar):
             _need_cuda("distance_affine", t)
-        prob.w_dist, prob.b_dist, prob.scalar = _ptr(w_dist), _ptr(b_dist), _ptr(scalar)
-    prob.anneal_rate = float(cfg.anneal_rate)
-    prob.two_level = int(cfg.two_level)
     if not cfg.two_level:
         if cfg.rich_calibrated_combine not in ("fixed", "trainable"):
             raise KeyError(cfg.rich_calibrated_combine)  # layers.py:935-936
-        prob.rich_combine = _lib.RICH[cfg.rich_calibrated_combine]
         if cfg.rich_calibrated_combine == "trainable":
             _need_cuda("rich_ratio", rich_ratio)
-            prob.rich_ratio = _ptr(rich_ratio)
-    # randomness
-    prob.p_drop = float(p_drop)
+            kw.update(rich_ratio=rich_ratio)
+        kw.update(rich=cfg.rich_calibrated_combine)
     if rnd is not None:
-        prob.rng_mode = _lib.RNG_EXPLICIT
         shape = (B, cfg.n_heads, L, L)
         if rnd.noise is not None:
             _need_cuda("noise", rnd.noise)
             assert rnd.noise.shape == shape
-            prob.noise = _ptr(rnd.noise)
+        keeps = []
         for field in ("keep_after", "keep_mask", "keep_before"):
             t = getattr(rnd, field)
             if t is not None:
@@ -159,16 +133,14 @@ def _fill_problem(q, k, v, qa, ka, gate_logits, mask, w_order, b_order, w_dist, 
                     keepalive.append(t)
                 _need_cuda(field, t, torch.uint8)
                 assert t.shape == shape
-                setattr(prob, field, _ptr(t))
-        if p_drop > 0 and rnd.keep_after is None:
-            prob.p_drop = 0.0
-    else:
-        prob.rng_mode = _lib.RNG_COUNTER
-        prob.seed = seed & 0xFFFFFFFFFFFFFFFF
-        if seed_tensor is not None:
-            _need_cuda("seed_tensor", seed_tensor, torch.int64)
-            prob.seed_device = _ptr(seed_tensor)
-    return prob
+            keeps.append(t)
+        kw.update(rnd=(rnd.noise, *keeps))
+    elif seed_tensor is not None:
+        _need_cuda("seed_tensor", seed_tensor, torch.int64)
+    return attn_launch.fill_problem(q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar, cfg.n_heads, p_drop,
+                                    seed, seed_tensor, adversarial=cfg.adversarial, combine=cfg.combine_option,
+                                    gate_is_prob=gate_is_prob, affine=affine, two_level=cfg.two_level,
+                                    anneal_rate=float(cfg.anneal_rate), **kw)
 
 
 # Route the launches of the training form (structured mask, counter RNG, `gate`, two_level, both spatial terms, no
@@ -234,30 +206,13 @@ class _CalibratedAttention(torch.autograd.Function):
                 ctx_att = M = stats = pen = None
             if not want_pen:
                 pen = None
-            ctx.cfg, ctx.p_drop, ctx.rnd, ctx.seed, ctx.mask, ctx.seed_tensor = cfg, p_drop, rnd, seed, mask, seed_tensor
-            ctx.save_for_backward(q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar, rich_ratio, M, stats)
-            return (ctx_att, ctx_cal, M, None, None, None, None, pen)
-        prob = _fill_problem(q, k, v, qa, ka, gate_logits, mask, wo, b_order, wd, b_dist, scalar, rich_ratio, cfg,
-                             p_drop, rnd, seed, keep, seed_tensor, gate_is_prob, affine)
-        out = FwdOut()
-        ctx_cal = torch.empty_like(q)
-        out.ctx_calibrated = _ptr(ctx_cal)
-        ctx_att = M = stats = None
-        probs = {}
-        if cfg.adversarial:
-            ctx_att = torch.empty_like(q)
-            M = torch.empty(B, nh, L, L, device=q.device, dtype=torch.float32)
-            stats = torch.empty(B, nh, L, _lib.NSTAT, device=q.device, dtype=torch.float32)
-            out.ctx_attacked, out.attack_mask, out.row_stats = _ptr(ctx_att), _ptr(M), _ptr(stats)
-            if want_probs:
-                for name in ("after_spatial", "before_spatial", "perturbed_attention", "calibrated_attention"):
-                    probs[name] = torch.empty_like(M)
-                    setattr(out, name, _ptr(probs[name]))
-        pen = None
-        if PENALTY_ROWS and cfg.adversarial and any(ctx.needs_input_grad[:12]):
-            pen = torch.empty(B, nh, (L + 15) // 16, device=q.device, dtype=torch.float32)
-            out.penalty_part = _ptr(pen)  # filled by the launch itself or by acattn_mask_penalty_rows behind it
-        _lib.check(lib.acattn_calibrated_attention_fwd(C.byref(prob), C.byref(out), _stream()), "calibrated_attention_fwd")
+            probs = {}
+        else:
+            prob = _fill_problem(q, k, v, qa, ka, gate_logits, mask, wo, b_order, wd, b_dist, scalar, rich_ratio, cfg,
+                                 p_drop, rnd, seed, keep, seed_tensor, gate_is_prob, affine)
+            ctx_att, ctx_cal, M, stats, probs, pen = attn_launch.attention_fwd_launch(
+                lib, prob, q, nh, adversarial=cfg.adversarial, want_probs=want_probs,
+                want_penalty=bool(PENALTY_ROWS and any(ctx.needs_input_grad[:12])))
         ctx.cfg, ctx.p_drop, ctx.rnd, ctx.seed, ctx.mask, ctx.seed_tensor = cfg, p_drop, rnd, seed, mask, seed_tensor
         ctx.save_for_backward(q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar, rich_ratio, M, stats)
         outs = [ctx_att, ctx_cal, M] + [probs.get(n) for n in
@@ -274,58 +229,27 @@ class _CalibratedAttention(torch.autograd.Function):
         if not cfg.adversarial:
             return _CalibratedAttention._spatial_backward(ctx, d_cal)
         lib = _lib.load()
-        B, L, H = q.shape
-        nh, dh = cfg.n_heads, H // cfg.n_heads
+        nh, dh = cfg.n_heads, q.shape[2] // cfg.n_heads
         keep = []
         wo = w_order.reshape(-1) if w_order is not None else None
         wd = w_dist.reshape(-1) if w_dist is not None else None
-        d_att = None if d_att is None else d_att.contiguous()
-        d_cal = None if d_cal is None else d_cal.contiguous()
-        d_M = None if d_M is None else d_M.contiguous()
+        d_att, d_cal, d_M = (None if t is None else t.contiguous() for t in (d_att, d_cal, d_M))
         d_pen = _unused[4].contiguous() if len(_unused) > 4 and _unused[4] is not None else None
+        # pass 2 through a layer with nothing attack-related upstream: only the attack transforms' inputs matter
+        attack_only = ctx.state.attack_pass_only and not ctx.attack_upstream
         if ctx.via_dispatcher:
-            attack_only = ctx.state.attack_pass_only and not ctx.attack_upstream
-            dq, dk, dv, dqa, dka, dgate_part, part = torch.ops.acattn.calibrated_attention_bwd(
+            res = torch.ops.acattn.calibrated_attention_bwd(
                 q, k, v, qa, ka, gate_logits, ctx.mask.key_valid, bool(ctx.mask.causal), wo.contiguous(), b_order,
                 wd.contiguous(), b_dist, scalar, nh, float(ctx.p_drop), int(ctx.seed) & 0x7FFFFFFFFFFFFFFF, ctx.seed_tensor,
                 bool(ctx.gate_is_prob), M, stats, d_att, d_cal, d_M, ctx.read_rows, ctx.active_qblocks, bool(attack_only), d_pen)
-            return _CalibratedAttention._finish_backward(lib, attack_only, dq, dk, dv, dqa, dka, dgate_part, part, dh,
-                                                         w_order, b_order, w_dist, b_dist, scalar, rich_ratio, ctx.state)
-        prob = _fill_problem(q, k, v, qa, ka, gate_logits, ctx.mask, wo, b_order, wd, b_dist, scalar, rich_ratio, cfg,
-                             ctx.p_drop, ctx.rnd, ctx.seed, keep, ctx.seed_tensor, ctx.gate_is_prob)
-        io = BwdIO()
-        io.attack_mask, io.row_stats = _ptr(M), _ptr(stats)
-        io.d_ctx_attacked, io.d_ctx_calibrated, io.d_attack_mask = _ptr(d_att), _ptr(d_cal), _ptr(d_M)
-        io.d_penalty_part = _ptr(d_pen)
-        dq, dk, dv, dqa, dka = (torch.empty_like(q) for _ in range(5))
-        io.dq, io.dk, io.dv, io.dqa, io.dka = _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dqa), _ptr(dka)
-        dgate = dgate_part = None
-        if cfg.combine_option == "gate":
-            io.dgate_logits = _ptr(q)  # (placeholder for the query below: only tested for NULL)
-        # the three per-(b, head) partial sums share ONE [B*nh, 4*dh + 4] buffer, reduced in a single pass
-        width = 4 * dh + 4
-        part = torch.empty(B * nh, width, device=q.device, dtype=torch.float32)
-        ws_bytes = int(lib.acattn_calibrated_attention_bwd_workspace_bytes(C.byref(prob)))
-        ws = torch.empty(max(ws_bytes, 4) // 4, device=q.device, dtype=torch.float32)  # row scalars (streaming backward)
-        io.workspace = _ptr(ws)
-        base = part.data_ptr()
-        io.dw_order_part, io.dw_dist_part, io.dsmall_part = base, base + 4 * 2 * dh, base + 4 * 4 * dh
-        io.part_stride = width
-        # the context cotangents are zero outside the read positions (the caller's promise, `read_rows`)
-        # (with a mask cotangent every block stays active, but those without a read position only owe the mask path)
-        io.active_qblocks = _ptr(ctx.active_qblocks) if ctx.active_qblocks is not None else None
-        if ctx.read_rows is not None:
-            io.read_rows, io.n_read_rows = _ptr(ctx.read_rows), ctx.read_rows.shape[1]
-        # pass 2 through a layer with nothing attack-related upstream: only the attack transforms' inputs matter
-        attack_only = ctx.state.attack_pass_only and not ctx.attack_upstream
-        io.attack_only = int(attack_only)
-        if cfg.combine_option == "gate":
-            summed = bool(lib.acattn_calibrated_attention_bwd_gate_summed(C.byref(prob), C.byref(io)))  # see dispatch._bwd_cuda
-            dgate_part = torch.empty(B, 1 if summed else nh, L, L, device=q.device, dtype=torch.float32)
-            io.dgate_logits, io.dgate_summed = _ptr(dgate_part), int(summed)
-        _lib.check(lib.acattn_calibrated_attention_bwd(C.byref(prob), C.byref(io), _stream()), "calibrated_attention_bwd")
-        return _CalibratedAttention._finish_backward(lib, attack_only, dq, dk, dv, dqa, dka, dgate_part, part, dh, w_order,
-                                                     b_order, w_dist, b_dist, scalar, rich_ratio, ctx.state)
+        else:
+            prob = _fill_problem(q, k, v, qa, ka, gate_logits, ctx.mask, wo, b_order, wd, b_dist, scalar, rich_ratio, cfg,
+                                 ctx.p_drop, ctx.rnd, ctx.seed, keep, ctx.seed_tensor, ctx.gate_is_prob)
+            res = attn_launch.attention_bwd_launch(
+                lib, prob, q, nh, M, stats, d_att=d_att, d_cal=d_cal, d_M=d_M, d_pen=d_pen, read_rows=ctx.read_rows,
+                active_qblocks=ctx.active_qblocks, attack_only=attack_only, gate=cfg.combine_option == "gate")
+        return _CalibratedAttention._finish_backward(lib, attack_only, *res, dh, w_order, b_order, w_dist, b_dist, scalar,
+                                                     rich_ratio, ctx.state)
 
     @staticmethod
     def _spatial_backward(ctx, d_cal):
@@ -337,8 +261,7 @@ class _CalibratedAttention(torch.autograd.Function):
             return (None,) * 24
         cfg = ctx.cfg
         lib = _lib.load()
-        B, L, H = q.shape
-        nh, dh = cfg.n_heads, H // cfg.n_heads
+        nh, dh = cfg.n_heads, q.shape[2] // cfg.n_heads
         d_cal = d_cal.contiguous()
         read_rows = ctx.read_rows  # (more than four read positions are kept as a block bitmap, the adversarial kernels' form:
         #                            every block runs then, which the promise allows)
@@ -355,12 +278,7 @@ class _CalibratedAttention(torch.autograd.Function):
                                  ctx.rnd, ctx.seed, keep, ctx.seed_tensor)
             dq, dk, dv, part = spatial_attention_bwd_launch(lib, prob, q, d_cal, nh, read_rows)
         tot = sum_rows0(part, ctx.state)
-        small = tot[4 * dh:]
-        g_wo = tot[:2 * dh].view_as(w_order) if w_order is not None else None
-        g_bo = small[0:1].view_as(b_order) if w_order is not None else None
-        g_wd = tot[2 * dh:4 * dh].view_as(w_dist) if w_dist is not None else None
-        g_bd = small[1:2].view_as(b_dist) if w_dist is not None else None
-        g_sc = small[2:3].view_as(scalar) if w_dist is not None else None
+        g_wo, g_bo, g_wd, g_bd, g_sc, _ = attn_launch.unpack_partials(tot, dh, w_order, b_order, w_dist, b_dist, scalar)
         if ctx.state is not None:
             ctx.state.watch(tot, g_wo, g_bo, g_wd, g_bd, g_sc, None)
         return (dq, dk, dv, None, None, None, g_wo, g_bo, g_wd, g_bd, g_sc) + (None,) * 13
@@ -381,37 +299,20 @@ class _CalibratedAttention(torch.autograd.Function):
                 and ctx.read_rows is None and ctx.active_qblocks is None):
             return None
         (q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar, rich_ratio, M, stats) = ctx.saved_tensors
-        from . import dispatch
         lib = _lib.load()
-        B, L, H = q.shape
-        nh, dh = cfg.n_heads, H // cfg.n_heads
-        wo, wd = w_order.reshape(-1).contiguous(), w_dist.reshape(-1).contiguous()
-        prob = dispatch._problem(q, k, v, qa, ka, gate_logits, ctx.mask.key_valid, bool(ctx.mask.causal), wo, b_order, wd, b_dist,
-                                 scalar, nh, float(ctx.p_drop), int(ctx.seed) & 0x7FFFFFFFFFFFFFFF, ctx.seed_tensor,
-                                 bool(ctx.gate_is_prob), None, True)
-        io = BwdIO()
-        d_cal1 = d_cal1.contiguous()
-        d_cal2 = None if d_cal2 is None else d_cal2.contiguous()
-        d_pen2 = None if d_pen2 is None else d_pen2.contiguous()
-        io.attack_mask, io.row_stats = _ptr(M), _ptr(stats)
-        io.d_ctx_calibrated, io.d_ctx_calibrated2, io.d_penalty_part2 = _ptr(d_cal1), _ptr(d_cal2), _ptr(d_pen2)
-        dq, dk, dv, dqa, dka, dqa2, dka2 = (torch.empty_like(q) for _ in range(7))
-        io.dq, io.dk, io.dv, io.dqa, io.dka, io.dqa2, io.dka2 = (_ptr(t) for t in (dq, dk, dv, dqa, dka, dqa2, dka2))
-        dgate_part = torch.empty(B, nh, L, L, device=q.device, dtype=torch.float32)
-        io.dgate_logits = _ptr(dgate_part)
-        width = 4 * dh + 4
-        part = torch.empty(B * nh, width, device=q.device, dtype=torch.float32)
-        ws_bytes = int(lib.acattn_calibrated_attention_bwd_workspace_bytes(C.byref(prob)))
-        ws = torch.empty(max(ws_bytes, 4) // 4, device=q.device, dtype=torch.float32)
-        io.workspace = _ptr(ws)
-        base = part.data_ptr()
-        io.dw_order_part, io.dw_dist_part, io.dsmall_part = base, base + 4 * 2 * dh, base + 4 * 4 * dh
-        io.part_stride = width
-        if not lib.acattn_calibrated_attention_bwd_pair_supported(C.byref(prob), C.byref(io)):
-            return None  # (L <= 64: the row-resident kernel; head size 128; a pinned kernel)
-        _lib.check(lib.acattn_calibrated_attention_bwd(C.byref(prob), C.byref(io), _stream()), "calibrated_attention_bwd (pair)")
-        res_cal = _CalibratedAttention._finish_backward(lib, False, dq, dk, dv, dqa, dka, dgate_part, part, dh, w_order, b_order,
-                                                        w_dist, b_dist, scalar, rich_ratio)
+        nh, dh = cfg.n_heads, q.shape[2] // cfg.n_heads
+        prob = attn_launch.fill_problem(q, k, v, qa, ka, gate_logits, w_order.reshape(-1).contiguous(), b_order,
+                                        w_dist.reshape(-1).contiguous(), b_dist, scalar, nh, float(ctx.p_drop),
+                                        int(ctx.seed) & 0x7FFFFFFFFFFFFFFF, ctx.seed_tensor, key_valid=ctx.mask.key_valid,
+                                        causal=bool(ctx.mask.causal), gate_is_prob=bool(ctx.gate_is_prob))
+        res = attn_launch.attention_bwd_launch(
+            lib, prob, q, nh, M, stats, d_cal=d_cal1.contiguous(),
+            second=(None if d_cal2 is None else d_cal2.contiguous(), None if d_pen2 is None else d_pen2.contiguous()))
+        if res is None:
+            return None
+        dqa2, dka2 = res[7:]
+        res_cal = _CalibratedAttention._finish_backward(lib, False, *res[:7], dh, w_order, b_order, w_dist, b_dist, scalar,
+                                                        rich_ratio)
         res_att = (None, None, None, dqa2, dka2) + (None,) * 19
         return res_cal, res_att
 
@@ -439,13 +340,8 @@ class _CalibratedAttention(torch.autograd.Function):
                 # autograd on arrival, so they are not summed at all
                 return (dq, dk, dv, dqa, dka, dgate) + (None,) * 18
             tot = sum_rows0(part, state)
-        small = tot[4 * dh:]
-        g_wo = tot[:2 * dh].view_as(w_order) if w_order is not None else None
-        g_bo = small[0:1].view_as(b_order) if w_order is not None else None
-        g_wd = tot[2 * dh:4 * dh].view_as(w_dist) if w_dist is not None else None
-        g_bd = small[1:2].view_as(b_dist) if w_dist is not None else None
-        g_sc = small[2:3].view_as(scalar) if w_dist is not None else None
-        g_rr = small[3:4].view_as(rich_ratio) if rich_ratio is not None else None
+        g_wo, g_bo, g_wd, g_bd, g_sc, g_rr = attn_launch.unpack_partials(tot, dh, w_order, b_order, w_dist, b_dist, scalar,
+                                                                         rich_ratio)
         if state is not None:
             state.watch(tot, g_wo, g_bo, g_wd, g_bd, g_sc, g_rr)
         return (dq, dk, dv, dqa, dka, dgate, g_wo, g_bo, g_wd, g_bd, g_sc, g_rr, None, None, None, None, None, None, None,
@@ -488,33 +384,6 @@ def calibrated_attention(q, k, v, qa, ka, gate_logits, mask, cfg: AttentionConfi
     if outs[7] is not None:
         outs[2]._acattn_pen = outs[7]  # see PENALTY_ROWS
     return outs[0], outs[1], outs[2], probs
-
-
-def spatial_attention_bwd_launch(lib, prob: Problem, q, d_ctx, n_heads: int, read_rows=None, poison: bool = False):
-    """One acattn_spatial_attention_bwd call for a filled `prob` (adversarial == 0): allocates the outputs, the
-    [B * n_heads, 4 * dh + 4] parameter-partial buffer (layout of acattn_bwd_io) and the workspace.  Returns
-    (dq, dk, dv, part).  `poison`: outputs start as NaN (ACATTN_POISON_OUTPUTS, dispatch.py)."""
-    B, L, H = q.shape
-    dh = H // n_heads
-    poison = poison or os.environ.get("ACATTN_POISON_OUTPUTS") == "1"  # (the direct C-ABI form honours it as well)
-    new = (lambda *shape: torch.full(shape, float("nan"), device=q.device, dtype=torch.float32)) if poison else \
-        (lambda *shape: torch.empty(*shape, device=q.device, dtype=torch.float32))
-    io = SpatialBwdIO()
-    io.d_ctx = _ptr(d_ctx)
-    dq, dk, dv = new(B, L, H), new(B, L, H), new(B, L, H)
-    io.dq, io.dk, io.dv = _ptr(dq), _ptr(dk), _ptr(dv)
-    width = 4 * dh + 4
-    part = new(B * n_heads, width)
-    base = part.data_ptr()
-    io.dw_order_part, io.dw_dist_part, io.dsmall_part = base, base + 4 * 2 * dh, base + 4 * 4 * dh
-    io.part_stride = width
-    if read_rows is not None:
-        io.read_rows, io.n_read_rows = _ptr(read_rows), read_rows.shape[1]
-    ws_bytes = int(lib.acattn_spatial_attention_bwd_workspace_bytes(C.byref(prob)))
-    ws = torch.empty(max(ws_bytes, 4) // 4, device=q.device, dtype=torch.float32)
-    io.workspace = _ptr(ws)
-    _lib.check(lib.acattn_spatial_attention_bwd(C.byref(prob), C.byref(io), _stream()), "spatial_attention_bwd")
-    return dq, dk, dv, part
 
 
 def materialize_randomness(B: int, n_heads: int, L: int, seed: int, p_drop: float, device) -> ExplicitRandomness:

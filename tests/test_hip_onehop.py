@@ -298,6 +298,60 @@ def test_dispatcher_operators_equal_the_direct_c_abi_path():
                           test_utils=("test_schema", "test_faketensor"))
 
 
+# (L, H, heads, read-row columns, mask cotangent, attack_only) that the CUDA operator refuses with an error (none does)
+_GATE_SHAPE_EXPECTED_REFUSALS = set()
+
+
+def test_meta_shape_of_the_gate_gradient_equals_the_cuda_operators():
+    """acattn::calibrated_attention_bwd returns the gate gradient as [B,1,L,L] when the launch sums over the heads itself and
+    as [B,heads,L,L] when not.  The CUDA implementation asks the library (attn_launch.gate_summed), the Meta implementation
+    has no pointers and follows attn_launch.gate_summed_rule: under the default environment and ACATTN_BWD_AUTO both must
+    give the same shape for every operator-form case below (B = 4; the forward runs first so that attack_mask and row_stats
+    are real).  Only shapes are compared; the context cotangents are zero outside the read rows, as the operator asks."""
+    from ac_tsr_amd import dispatch  # noqa: F401
+    B = 4
+    lib = _lib.load()
+    pinned = lib.acattn_select_backward_kernel(_lib.BWD_AUTO)
+    bad, refused, n_cases = [], set(), 0
+    try:
+        for L in (37, 50, 64, 100, 200):
+            for H, nh in ((64, 2), (64, 4), (128, 2), (128, 1)):
+                t, kv, lens, g = _problem(B, L, H, nh, seed=L + H + nh)
+                fixed = [t[k] for k in ("q", "k", "v", "qa", "ka", "gl")] + [kv, True, t["w_order"].reshape(-1), t["b_order"],
+                                                                             t["w_dist"].reshape(-1), t["b_dist"], t["scalar"]]
+                on = lambda dev, xs: [x.to(dev) if isinstance(x, torch.Tensor) else x for x in xs]
+                tail = [nh, 0.5, 77, None, False]
+                out = torch.ops.acattn.calibrated_attention_fwd(*on(DEV, fixed), *tail, None, True)
+                last = (lens - 1).view(-1, 1)
+                for rows in (None, last, torch.cat([last, (lens - 2).clamp(min=0).view(-1, 1)], 1)):
+                    d_ctx = [torch.randn(B, L, H, generator=g) for _ in range(2)]
+                    if rows is not None:
+                        at_rows = torch.zeros(B, L, 1).scatter_(1, rows.unsqueeze(-1), 1.0)
+                        d_ctx = [d * at_rows for d in d_ctx]
+                    d_M, d_pen = torch.randn(B, nh, L, L, generator=g), torch.randn(B, nh, (L + 15) // 16, generator=g)
+                    for cot, mask_cot in (("none", (None, None)), ("d_attack_mask", (d_M, None)), ("d_penalty_part", (None, d_pen))):
+                        for attack_only in (False, True):
+                            case = (L, H, nh, 0 if rows is None else rows.shape[1], cot, attack_only)
+                            n_cases += 1
+                            args = lambda dev, M, stats: (*on(dev, fixed), *tail, M, stats, *on(dev, d_ctx), *on(dev, [mask_cot[0], rows]),
+                                                          None, attack_only, *on(dev, [mask_cot[1]]))
+                            meta = torch.ops.acattn.calibrated_attention_bwd(*args("meta", out[2].to("meta"), out[3].to("meta")))
+                            try:
+                                cuda = torch.ops.acattn.calibrated_attention_bwd(*args(DEV, out[2], out[3]))
+                            except (_lib.AcattnError, TypeError, ValueError):
+                                refused.add(case)
+                                continue
+                            print(case, "meta", tuple(meta[5].shape), "cuda", tuple(cuda[5].shape))
+                            if [m.shape for m in meta] != [c.shape for c in cuda]:
+                                bad.append((case, tuple(meta[5].shape), tuple(cuda[5].shape)))
+                torch.cuda.synchronize()
+    finally:
+        lib.acattn_select_backward_kernel(pinned)
+    assert n_cases == 5 * 4 * 3 * 3 * 2
+    assert refused == _GATE_SHAPE_EXPECTED_REFUSALS, refused ^ _GATE_SHAPE_EXPECTED_REFUSALS
+    assert not bad, bad
+
+
 def test_dispatcher_operators_reject_what_the_c_abi_would_misread():
     """The operators hand raw pointers to the C ABI (fp32 / uint8, exact shapes): a half-precision activation (autocast), an
     int64 validity mask, a gate or affine of another length, a tensor on the host must raise, not be reinterpreted

@@ -25,7 +25,7 @@ import pytest
 import torch
 
 import ac_tsr_amd as A
-from ac_tsr_amd import dispatch, ops
+from ac_tsr_amd import attn_launch, dispatch, ops  # noqa: F401  (dispatch: registers torch.ops.acattn.*)
 from oracle import ac_tsr_ref as O
 
 pytestmark = pytest.mark.gpu
@@ -206,7 +206,7 @@ def test_poisoned_outputs_are_fully_written(terms, monkeypatch):
     """ACATTN_POISON_OUTPUTS=1: every output buffer starts as NaN; a disabled term's partial columns, the spare column and
     the dq rows of skipped query blocks must have been written (as zeros)."""
     monkeypatch.setenv("ACATTN_POISON_OUTPUTS", "1")
-    monkeypatch.setattr(dispatch, "_POISON", True)
+    monkeypatch.setattr(attn_launch, "POISON", True)
     B, L, H, nh = 8, 50, 64, 2
     t, kv, lens, dense, mask_dev, seed, keep, rnd, G, dead = _setup(B, L, H, nh, "structured", True, True, 0.5, 0.3, "counter")
     rows = (lens - 1).view(-1, 1)
