@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("ACATTN_LIB") or os.path.join(CSRC, "libacattn.so")  # ACATTN_LIB: experiments only
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "acattn.h")
 
-ABI_VERSION = 32
+ABI_VERSION = 33
 MAX_MASKS = 8  # ACATTN_MAX_MASKS
 NSTAT = 8
 MASK_STRUCTURED, MASK_DENSE_LL, MASK_DENSE_L = 0, 1, 2
@@ -87,7 +87,7 @@ class ProjProblem(C.Structure):
     _fields_ = [("rows", C.c_int32), ("H", C.c_int32), ("G", C.c_int32), ("x", _f), ("wq", _f), ("bq", _f), ("wk", _f),
                 ("bk", _f), ("wv", _f), ("bv", _f), ("waq", _f), ("baq", _f), ("wak", _f), ("bak", _f), ("wg", _f),
                 ("bg", _f), ("w_order", _f), ("b_order", _f), ("w_dist", _f), ("b_dist", _f), ("n_heads", C.c_int32),
-                ("L", C.c_int32)]
+                ("L", C.c_int32), ("split_planes", _f)]
 
 
 class ProjOut(C.Structure):
@@ -115,6 +115,14 @@ class TailProblem(C.Structure):
                 ("eps1", C.c_float), ("eps2", C.c_float), ("p1", C.c_float), ("p2", C.c_float), ("keep1", _f),
                 ("keep2", _f), ("seed1", C.c_uint64), ("seed2", C.c_uint64), ("seed_device", _f), ("src_index", _f),
                 ("src_R", C.c_int32), ("src_L", C.c_int32), ("split_planes", _f)]
+
+
+SPLIT_MAX_LAYERS = 8
+
+
+class SplitLayer(C.Structure):
+    _fields_ = [("wd", _f), ("w1", _f), ("w2", _f), ("I", C.c_int32), ("tail_planes", _f), ("wq", _f), ("wk", _f),
+                ("wv", _f), ("waq", _f), ("wak", _f), ("wg", _f), ("G", C.c_int32), ("proj_planes", _f)]
 
 
 class TailSaved(C.Structure):
@@ -176,6 +184,8 @@ SYMBOLS = {
     "acattn_select_layer_tail_blocks": (C.c_int, [C.c_int]),
     "acattn_layer_tail_split_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "acattn_layer_tail_split_weights": (C.c_int, [C.POINTER(TailProblem), C.c_void_p, C.c_void_p]),
+    "acattn_split_weights_many": (C.c_int, [C.POINTER(SplitLayer), C.c_int32, C.c_void_p]),
+    "acattn_projections_split_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "acattn_adam_step": (C.c_int, [C.POINTER(AdamGroup), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _f,
                                    C.c_void_p]),
     "acattn_dense_ce_fwd": (C.c_int, [_f, C.c_int64, C.c_int64, _f, _f, _f, C.c_void_p]),

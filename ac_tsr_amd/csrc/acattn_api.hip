@@ -243,6 +243,7 @@ static int check_proj(const acattn_proj_problem* p) {
     return fail("projections: input and parameters must be non-NULL");
   if ((p->wg != nullptr) != (p->bg != nullptr) || (p->wg != nullptr) != (p->G > 0))
     return fail("projections: gate weight, bias and width go together");
+  if (((uintptr_t)p->split_planes & 15) != 0) return fail("projections: split_planes must be 16-byte aligned");
   return 0;
 }
 
@@ -326,6 +327,27 @@ int acattn_layer_tail_split_weights(const acattn_tail_problem* p, void* planes, 
   if (p->H != 64 || (p->I != 256 && p->I != 128)) return fail("layer tail split planes: hidden 64, inner 256 or 128 only");
   if (((uintptr_t)planes & 15) != 0) return fail("layer tail split planes: planes must be 16-byte aligned");
   const int rc = acattn_launch_tail_split(*p, planes, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
+int64_t acattn_projections_split_bytes(int32_t H, int32_t G) { return acattn_proj_split_bytes(H, G); }
+
+int acattn_split_weights_many(const acattn_split_layer* layers, int32_t n_layers, void* stream) {
+  if (!layers || n_layers < 1 || n_layers > ACATTN_SPLIT_MAX_LAYERS) return fail("split planes: 1 .. ACATTN_SPLIT_MAX_LAYERS layers");
+  for (int k = 0; k < n_layers; ++k) {
+    const acattn_split_layer& l = layers[k];
+    if (l.tail_planes) {
+      if (!l.wd || !l.w1 || !l.w2) return fail("split planes: tail planes need wd, w1 and w2");
+      if (l.I != 256 && l.I != 128) return fail("split planes: tail planes are for hidden 64, inner 256 or 128");
+    }
+    if (l.proj_planes) {
+      if (!l.wq || !l.wk || !l.wv || !l.waq || !l.wak) return fail("split planes: projection planes need the five square weights");
+      if ((l.wg != nullptr) != (l.G > 0) || l.G < 0 || l.G > 64) return fail("split planes: gate weight and width go together, at most 64 outputs");
+    }
+    if ((((uintptr_t)l.tail_planes | (uintptr_t)l.proj_planes) & 15) != 0) return fail("split planes: planes must be 16-byte aligned");
+  }
+  const int rc = acattn_launch_split_many(layers, n_layers, (hipStream_t)stream);
   if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
   return rc;
 }

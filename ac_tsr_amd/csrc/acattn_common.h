@@ -345,6 +345,7 @@ void acattn_set_error(const char* msg);
 bool acattn_proj_supported(int H, int G);
 int64_t acattn_proj_bwd_ws_bytes(const acattn_proj_problem& p);
 int acattn_launch_proj_fwd(const acattn_proj_problem& p, const acattn_proj_out& o, hipStream_t stream);
+int64_t acattn_proj_split_bytes(int H, int G);
 bool acattn_proj_qkv_supported(int H);
 int acattn_launch_proj_qkv_fwd(const acattn_proj_problem& p, const acattn_proj_out& o, hipStream_t stream);
 int acattn_launch_proj_bwd(const acattn_proj_problem& p, const acattn_proj_bwd_io& io, hipStream_t stream);
@@ -355,6 +356,7 @@ int64_t acattn_tail_bwd_ws_bytes(int H, int I);
 int acattn_select_tail_nb(int nb);
 int64_t acattn_tail_split_bytes(int H, int I, int rows);
 int acattn_launch_tail_split(const acattn_tail_problem& p, void* planes, hipStream_t stream);
+int acattn_launch_split_many(const acattn_split_layer* layers, int n_layers, hipStream_t stream);
 int acattn_launch_tail_fwd(const acattn_tail_problem& p, const acattn_tail_saved& s, hipStream_t stream);
 int acattn_launch_tail_bwd(const acattn_tail_problem& p, const acattn_tail_saved& s, const acattn_tail_bwd_io& io,
                            hipStream_t stream);

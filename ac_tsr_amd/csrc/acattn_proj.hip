@@ -962,10 +962,14 @@ __global__ void __launch_bounds__(64 * NWV, 2) proj_staged_bwd_kernel(const acat
 //   [matrix][tile][s][plane][lane] fragments, every wave reads all of them back with ds_read_b128 (conflict-free).  The
 //   six matrices take 144 KB, so the gate (one matrix of the six) must have G <= 64 outputs; wider gates stay on
 //   proj_fwd_kernel / proj_bwd_kernel.
+//   With acattn_proj_problem.split_planes the same fragments, split once per encoder forward by split_many_kernel
+//   (acattn_tail.hip), are read from global memory instead (proj_planes_fwd_kernel / proj_planes_bwd_kernel, below the
+//   LDS kernels): no LDS image, no barrier, one wave per workgroup; DESIGN.md 4.6.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int SPW = 4;                                       // waves per workgroup (one per output tile)
-constexpr int SPLIT_MAT = 4 * 2 * 3 * 64;                    // b8 per matrix: [tile][s][plane][lane]
+constexpr int SPLIT_MAT = SPLIT_SQ64;                        // b8 per matrix: [tile][s][plane][lane]
 constexpr int SPLIT_LDS = 6 * SPLIT_MAT * (int)sizeof(b8);  // bytes
+static_assert(6 * SPLIT_MAT == PROJ_PLANES_DIR, "the planes image of one direction is the LDS image");
 
 __device__ __forceinline__ int kperm(int s, int g, int j) { return 32 * s + 16 * (j >> 2) + 4 * g + (j & 3); }
 
@@ -1250,6 +1254,264 @@ __global__ void __launch_bounds__(64 * SPW) proj_split_bwd_kernel(const acattn_p
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The split chains on the planes of acattn_proj_problem.split_planes: the fragments above, written once per
+// encoder forward by split_many_kernel (acattn_tail.hip), read from global memory.  No LDS image, no split of the weights,
+// no barrier; one wave per workgroup.  Same products in the same MFMA order per accumulator as the LDS kernels: every
+// tensor written is bitwise theirs.  (The LDS kernels keep their own text: routed through these chains their register
+// allocation changed -- proj_split_bwd_kernel<2, 0> 192 + 36 -> 220 + 68 -- and NULL planes must select them as they were.)
+// `product(next, ..)`: the product with the matrix in the ring; `next` names the matrix of the product that follows it in
+// the chain (-1: none), `begin(m)` the first one.
+// ---------------------------------------------------------------------------------------------------------------------
+// The planes in global memory (L2): one matrix (24 fragments) is in registers or on its way.  Every tile's six fragments
+// are requested for the NEXT product as soon as this product's MFMAs of that tile are issued, so a request has three
+// tiles of matrix work and the split of the next operand to arrive.  Same MFMA order per accumulator as split_product.
+struct PlaneWeights {
+  const b8* img;
+  int lane;
+  b8 ring[4][2][3];
+  __device__ __forceinline__ void fetch(int m, int nt) {
+    const b8* mat = img + (size_t)m * SPLIT_MAT + lane;
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) ring[nt][s][q] = mat[((nt * 2 + s) * 3 + q) * 64];
+  }
+  __device__ __forceinline__ void begin(int m) {
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) fetch(m, nt);
+  }
+  template <int NB>
+  __device__ __forceinline__ void product(int next, const b8 (&b)[NB][2][3], f4 (&acc)[NB][4]) {
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      PIN_ORDER();
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb][nt] = mfma_split(ring[nt][s], b[nb][s], acc[nb][nt]);
+      if (next >= 0) fetch(next, nt);  // (the scheduler would sink the requests to their use: pinned behind the tile)
+      PIN_ORDER();
+    }
+  }
+};
+
+// The same interface on an LDS image of the planes (proj_fill_bwd_kernel): a fragment is read where it is used.
+struct LdsImage {
+  const b8* img;
+  int lane, cur;
+  __device__ __forceinline__ void begin(int m) {
+    cur = m;
+    __syncthreads();  // the image is complete
+  }
+  template <int NB>
+  __device__ __forceinline__ void product(int next, const b8 (&b)[NB][2][3], f4 (&acc)[NB][4]) {
+    split_product<NB>(img + cur * SPLIT_MAT, lane, b, acc);
+    cur = next;
+  }
+};
+
+// proj_split_fwd_kernel's chain; matrices of the forward image: Wq, Waq, Wg, Wk, Wak, Wv (product k of the chain uses matrix k)
+template <int NB>
+__device__ __forceinline__ void split_fwd_chain(const acattn_proj_problem& P, const acattn_proj_out& O, const Rows<NB>& W,
+                                                PlaneWeights& ws, int c, int g) {
+  const bool gate = P.wg != nullptr;
+  f4 xb[NB][4], m[NB][4], acc[NB][4];
+  b8 xs[NB][2][3], ms[NB][2][3];
+  f4 bias[4];
+  load_rows<4, NB>(P.x, W, g, xb);
+  load_bias<4>(P.bq, g, bias);
+  ws.begin(0);  // (behind the rows: their split is the first thing to wait)
+  split_rows<NB>(xb, xs);
+  set_rows<4, NB>(bias, m);
+  ws.product<NB>(1, xs, m);  // mq
+  store_rows<4, NB>(O.mq, W, g, m);
+  if (O.affine) write_affine<4, NB>(m, W, P, O.affine, 0, P.b_order[0], P.b_dist[0], 0, c, g);
+  split_rows<NB>(m, ms);
+  load_bias<4>(P.baq, g, bias);
+  set_rows<4, NB>(bias, acc);
+  ws.product<NB>(gate ? 2 : 3, ms, acc);  // qa
+  store_rows<4, NB>(O.qa, W, g, acc);
+  if (gate) {
+    const int GT = (P.G + 15) >> 4;  // 1 .. 4
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      f4 b;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) b[r] = P.bg[min(16 * nt + 4 * g + r, P.G - 1)];
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) acc[nb][nt] = b;
+    }
+    ws.product<NB>(3, ms, acc);  // gate logits (tiles past G are computed and dropped)
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+      if (nt >= GT) break;
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        f4 v = acc[nb][nt];
+        if (O.gate_prob) v = gate_value(v, 0);  // sigmoid once per (b, i, j): the heads share it (layers.py:887)
+        const int j0 = 16 * nt + 4 * g;
+        float* dst = O.gate + (size_t)W.row[nb] * P.G + j0;
+        if (W.ok[nb] && j0 + 3 < P.G) {
+          *(f4u*)dst = v;
+        } else if (W.ok[nb]) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (j0 + r < P.G) dst[r] = v[r];
+        }
+      }
+    }
+  }
+  load_bias<4>(P.bk, g, bias);
+  set_rows<4, NB>(bias, m);
+  ws.product<NB>(4, xs, m);  // mk
+  store_rows<4, NB>(O.mk, W, g, m);
+  if (O.affine) write_affine<4, NB>(m, W, P, O.affine, 64 / P.n_heads, 0.f, 0.f, 2, c, g);
+  split_rows<NB>(m, ms);
+  load_bias<4>(P.bak, g, bias);
+  set_rows<4, NB>(bias, acc);
+  ws.product<NB>(5, ms, acc);  // ka
+  store_rows<4, NB>(O.ka, W, g, acc);
+  load_bias<4>(P.bv, g, bias);
+  set_rows<4, NB>(bias, acc);
+  ws.product<NB>(-1, xs, acc);  // mv
+  store_rows<4, NB>(O.mv, W, g, acc);
+}
+
+// The same chain on the planes of acattn_proj_problem.split_planes: one wave per workgroup, nothing shared.  Two waves fit
+// a SIMD (198 registers at NB = 1, 256 at NB = 2).
+template <int NB>
+__global__ void __launch_bounds__(64, 2) proj_planes_fwd_kernel(const acattn_proj_problem P, const acattn_proj_out O) {
+  const int lane = threadIdx.x, c = lane & 15, g = lane >> 4;
+  const Rows<NB> W = wave_rows<NB>(P.rows);
+  PlaneWeights ws;
+  ws.img = (const b8*)P.split_planes;
+  ws.lane = lane;
+  split_fwd_chain<NB>(P, O, W, ws, c, g);
+}
+
+// proj_split_bwd_kernel's chain; matrices of the backward image (transposed): Waq, Wg, Wq, Wak, Wk, Wv.  MODE as in
+// proj_bwd_kernel.
+template <int MODE>
+struct SplitBwdFlags {
+  bool h_dmq, h_dmk, h_dmv, h_dqa, h_dka, h_dx, h_qt, h_kt, gate;
+  __device__ __forceinline__ SplitBwdFlags(const acattn_proj_problem& P, const acattn_proj_bwd_io& IO)
+      : h_dmq(MODE == 1 || (MODE == 0 && IO.dmq)), h_dmk(MODE == 1 || (MODE == 0 && IO.dmk)),
+        h_dmv(MODE == 1 || (MODE == 0 && IO.dmv)), h_dqa(MODE != 0 || IO.dqa), h_dka(MODE != 0 || IO.dka),
+        h_dx(MODE != 0 || IO.dx), h_qt(MODE != 0 || IO.dmq_total), h_kt(MODE != 0 || IO.dmk_total),
+        gate(MODE != 2 && IO.dgate && P.wg) {}
+  // the first matrix behind `m` that a product of this launch uses, -1 = none (m = -1: the first of all)
+  __device__ __forceinline__ int next(int m) const {
+    const bool need[6] = {h_dqa, gate, h_dx, h_dka, h_dx, h_dx && h_dmv};
+    int n = -1;
+#pragma unroll
+    for (int j = 5; j >= 0; --j)
+      if (j > m && need[j]) n = j;
+    return n;
+  }
+};
+
+template <int NB, int MODE, class WS>
+__device__ __forceinline__ void split_bwd_chain(const acattn_proj_problem& P, const acattn_proj_bwd_io& IO, const Rows<NB>& W,
+                                                const SplitBwdFlags<MODE>& F, WS& ws, int g) {
+  const bool h_dmq = F.h_dmq, h_dmk = F.h_dmk, h_dmv = F.h_dmv, h_dqa = F.h_dqa, h_dka = F.h_dka, h_dx = F.h_dx;
+  const bool h_qt = F.h_qt, h_kt = F.h_kt, gate = F.gate;
+  auto zero = [&](f4 (&v)[NB][4]) {
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) v[nb][t] = f4{0.f, 0.f, 0.f, 0.f};
+  };
+  f4 in[NB][4], dq[NB][4], dk[NB][4], dx[NB][4];
+  b8 bs[NB][2][3];
+  if (IO.dx_init && h_dx) load_rows<4, NB>(IO.dx_init, W, g, dx); else zero(dx);  // the residual path's share of dx
+  if (h_dmq) load_rows<4, NB>(IO.dmq, W, g, dq); else zero(dq);
+  if (h_dqa) load_rows<4, NB>(IO.dqa, W, g, in);
+  const int first = F.next(-1);
+  if (first >= 0) ws.begin(first);  // (behind the rows: their split is the first thing to wait)
+
+  // ---- d mq (total) = dmq + dqa . Waq + dgate . Wg;  dx += d mq . Wq ------------------------------------------------
+  if (h_dqa) {
+    split_rows<NB>(in, bs);
+    ws.template product<NB>(F.next(0), bs, dq);
+  }
+  if (gate) {
+    // B[k][row c] = dgate[row][k], k = kperm(s, g, j) < G (G <= 64; rows of G floats: dword reads)
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        float x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int k = kperm(s, g, j);
+          const float t = IO.dgate[(size_t)W.row[nb] * P.G + min(k, P.G - 1)];
+          x[j] = k < P.G ? t : 0.f;
+        }
+        split8(x, bs[nb][s][0], bs[nb][s][1], bs[nb][s][2]);
+      }
+    ws.template product<NB>(F.next(1), bs, dq);
+  }
+  if (h_qt) store_rows<4, NB>(IO.dmq_total, W, g, dq);
+  if (h_dx) {
+    split_rows<NB>(dq, bs);
+    ws.template product<NB>(F.next(2), bs, dx);
+  }
+
+  // ---- d mk (total) = dmk + dka . Wak;  dx += d mk . Wk + d mv . Wv ---------------------------------------------------
+  if (h_dmk) load_rows<4, NB>(IO.dmk, W, g, dk); else zero(dk);
+  if (h_dka) {
+    load_rows<4, NB>(IO.dka, W, g, in);
+    split_rows<NB>(in, bs);
+    ws.template product<NB>(F.next(3), bs, dk);
+  }
+  if (h_kt) store_rows<4, NB>(IO.dmk_total, W, g, dk);
+  if (h_dx) {
+    split_rows<NB>(dk, bs);
+    ws.template product<NB>(F.next(4), bs, dx);
+    if (h_dmv) {
+      load_rows<4, NB>(IO.dmv, W, g, in);
+      split_rows<NB>(in, bs);
+      ws.template product<NB>(-1, bs, dx);
+    }
+    store_rows<4, NB>(IO.dx, W, g, dx);
+  }
+}
+
+// The same chain on the backward image of acattn_proj_problem.split_planes (see proj_planes_fwd_kernel).  Four row sets,
+// the split operand and the ring: 202 registers at NB = 1 (two waves per SIMD), 308 + 68 at NB = 2 (one).
+template <int NB, int MODE>
+__global__ void __launch_bounds__(64, NB == 1 ? 2 : 1) proj_planes_bwd_kernel(const acattn_proj_problem P, const acattn_proj_bwd_io IO) {
+  const SplitBwdFlags<MODE> F(P, IO);
+  const int lane = threadIdx.x, g = lane >> 4;
+  const Rows<NB> W = wave_rows<NB>(P.rows);
+  PlaneWeights ws;
+  ws.img = (const b8*)P.split_planes + PROJ_PLANES_DIR;
+  ws.lane = lane;
+  split_bwd_chain<NB, MODE>(P, IO, W, F, ws, g);
+}
+
+// The fallback form of the backward: the workgroups of proj_split_bwd_kernel, their LDS image filled from the planes with
+// straight 16-byte copies (no gathers, no split8), then the chain on the image.
+template <int NB, int MODE>
+__global__ void __launch_bounds__(64 * SPW) proj_fill_bwd_kernel(const acattn_proj_problem P, const acattn_proj_bwd_io IO) {
+  extern __shared__ b8 wsp[];
+  const SplitBwdFlags<MODE> F(P, IO);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  const Rows<NB> W = split_rows_of<NB>(P.rows, wave);
+  const b8* src = (const b8*)P.split_planes + PROJ_PLANES_DIR;
+  const bool need[6] = {F.h_dqa, F.gate, F.h_dx, F.h_dka, F.h_dx, F.h_dx && F.h_dmv};
+#pragma unroll
+  for (int m = 0; m < 6; ++m)
+    if (need[m]) {
+#pragma unroll
+      for (int i = 0; i < SPLIT_MAT / (64 * SPW); ++i)
+        wsp[m * SPLIT_MAT + i * 64 * SPW + threadIdx.x] = src[m * SPLIT_MAT + i * 64 * SPW + threadIdx.x];
+    }
+  LdsImage ws{wsp, lane, 0};
+  split_bwd_chain<NB, MODE>(P, IO, W, F, ws, g);
+}
+
 int rows_per_wave(int rows) {
   static const int forced = getenv("ACATTN_PROJ_ROWS_PER_WAVE") ? atoi(getenv("ACATTN_PROJ_ROWS_PER_WAVE")) : 0;  // measurements
   if (forced == 16 || forced == 32) return forced;
@@ -1343,6 +1605,10 @@ int linear_products() {
   return g_linear_products;
 }
 bool use_split(const acattn_proj_problem& p) { return p.H == 64 && (!p.wg || p.G <= 64) && linear_products() == 1; }
+int64_t proj_split_bytes(int H, int G) {
+  if (H != 64 || G < 0 || G > 64 || linear_products() != 1) return 0;
+  return (int64_t)2 * PROJ_PLANES_DIR * (int64_t)sizeof(b8);
+}
 
 // the dynamic LDS of a split kernel is above the 64 KB default: raised once per kernel
 template <class K>
@@ -1367,7 +1633,50 @@ int launch_split_bwd(const acattn_proj_problem& p, const acattn_proj_bwd_io& io,
   hipLaunchKernelGGL((proj_split_bwd_kernel<NB, MODE>), dim3(wgs), dim3(64 * SPW), SPLIT_LDS, stream, p, io);
   return (int)hipGetLastError();
 }
+
+// rows per wave of the planes kernels (16 * NB).  Measured per direction at 25,600 rows: forward 19.0 us
+// with 32 against 19.3 with 16, backward 18.35 against 19.1 -- twice the waves do not pay for twice the fragment traffic;
+// below 16,384 rows one row block, as the LDS kernels.  ACATTN_PROJ_PLANES_ROWS_FWD / _BWD = 16 | 32: measurements.
+int planes_rows_per_wave(int rows, bool bwd) {
+  static const int forced[2] = {getenv("ACATTN_PROJ_PLANES_ROWS_FWD") ? atoi(getenv("ACATTN_PROJ_PLANES_ROWS_FWD")) : 0,
+                                getenv("ACATTN_PROJ_PLANES_ROWS_BWD") ? atoi(getenv("ACATTN_PROJ_PLANES_ROWS_BWD")) : 0};
+  if (forced[bwd] == 16 || forced[bwd] == 32) return forced[bwd];
+  return rows >= 16384 ? 32 : 16;
+}
+
+template <int NB>
+int launch_planes_fwd(const acattn_proj_problem& p, const acattn_proj_out& o, hipStream_t stream) {
+  const int blocks = (p.rows + 16 * NB - 1) / (16 * NB);
+  hipLaunchKernelGGL((proj_planes_fwd_kernel<NB>), dim3(blocks), dim3(64), 0, stream, p, o);
+  return (int)hipGetLastError();
+}
+
+template <int NB, int MODE>
+int launch_planes_bwd(const acattn_proj_problem& p, const acattn_proj_bwd_io& io, hipStream_t stream) {
+  const int blocks = (p.rows + 16 * NB - 1) / (16 * NB);
+  hipLaunchKernelGGL((proj_planes_bwd_kernel<NB, MODE>), dim3(blocks), dim3(64), 0, stream, p, io);
+  return (int)hipGetLastError();
+}
+
+template <int NB, int MODE>
+int launch_fill_bwd(const acattn_proj_problem& p, const acattn_proj_bwd_io& io, hipStream_t stream) {
+  static const bool lds_ok = allow_split_lds(proj_fill_bwd_kernel<NB, MODE>);
+  if (!lds_ok) return (int)hipErrorInvalidValue;
+  const int wgs = (p.rows + 16 * NB * SPW - 1) / (16 * NB * SPW);
+  hipLaunchKernelGGL((proj_fill_bwd_kernel<NB, MODE>), dim3(wgs), dim3(64 * SPW), SPLIT_LDS, stream, p, io);
+  return (int)hipGetLastError();
+}
+
+// which backward reads the planes: 0 the direct-from-L2 kernel, 1 the LDS image filled from them, 2 none (the LDS kernel that
+// splits for itself).  ACATTN_PROJ_PLANES_BWD = direct | fill | lds: measurements.
+int planes_bwd_form() {
+  static const char* e = getenv("ACATTN_PROJ_PLANES_BWD");
+  static const int form = !e ? 0 : !strcmp(e, "fill") ? 1 : !strcmp(e, "lds") ? 2 : 0;
+  return form;
+}
 }  // namespace
+
+int64_t acattn_proj_split_bytes(int H, int G) { return proj_split_bytes(H, G); }
 
 int acattn_linear_products_choice(int mode) {
   const int old = linear_products();
@@ -1379,6 +1688,9 @@ int acattn_launch_proj_fwd(const acattn_proj_problem& p, const acattn_proj_out& 
   if (p.H == 128) return launch_wide_fwd<128>(p, o, stream);
   if (p.H == 256) return launch_wide_fwd<256>(p, o, stream);
   const int rpw = rows_per_wave(p.rows), blocks = (p.rows + rpw - 1) / rpw;
+  // (planes given where the split kernels do not run -- the product mode changed since they were made: they are not read)
+  if (p.split_planes && use_split(p))
+    return planes_rows_per_wave(p.rows, false) == 32 ? launch_planes_fwd<2>(p, o, stream) : launch_planes_fwd<1>(p, o, stream);
   if (use_split(p)) return rpw == 32 ? launch_split_fwd<2>(p, o, stream) : launch_split_fwd<1>(p, o, stream);
   if (rpw == 32)
     hipLaunchKernelGGL((proj_fwd_kernel<64, 2>), dim3(blocks), dim3(64), 0, stream, p, o);
@@ -1419,6 +1731,26 @@ int acattn_launch_proj_bwd(const acattn_proj_problem& p, const acattn_proj_bwd_i
   const bool all_in = attack && io.dmq && io.dmk && io.dmv && (io.dgate || !p.wg);
   const bool attack_only = attack && !io.dmq && !io.dmk && !io.dmv && !io.dgate;
   const int mode = !outs ? 0 : all_in ? 1 : attack_only ? 2 : 0;
+  if (p.split_planes && use_split(p) && planes_bwd_form() == 1) {
+    if (rpw == 32) {
+      if (mode == 1) return launch_fill_bwd<2, 1>(p, io, stream);
+      if (mode == 2) return launch_fill_bwd<2, 2>(p, io, stream);
+      return launch_fill_bwd<2, 0>(p, io, stream);
+    }
+    if (mode == 1) return launch_fill_bwd<1, 1>(p, io, stream);
+    if (mode == 2) return launch_fill_bwd<1, 2>(p, io, stream);
+    return launch_fill_bwd<1, 0>(p, io, stream);
+  }
+  if (p.split_planes && use_split(p) && planes_bwd_form() == 0) {
+    if (planes_rows_per_wave(p.rows, true) == 32) {
+      if (mode == 1) return launch_planes_bwd<2, 1>(p, io, stream);
+      if (mode == 2) return launch_planes_bwd<2, 2>(p, io, stream);
+      return launch_planes_bwd<2, 0>(p, io, stream);
+    }
+    if (mode == 1) return launch_planes_bwd<1, 1>(p, io, stream);
+    if (mode == 2) return launch_planes_bwd<1, 2>(p, io, stream);
+    return launch_planes_bwd<1, 0>(p, io, stream);
+  }
   if (use_split(p)) {
     if (rpw == 32) {
       if (mode == 1) return launch_split_bwd<2, 1>(p, io, stream);

@@ -33,6 +33,12 @@ __device__ __forceinline__ void split8(const float (&x)[8], b8& p0, b8& p1, b8& 
   }
 }
 
+// A 64 x 64 weight as A-operand fragments [tile][K-block s][plane][lane] of 16 bytes (K-block s of lane (c, g) holds
+// the features 32 s + 16 (j >> 2) + 4 g + (j & 3), j = 0..7), in b8 elements; the planes of the six projections of one
+// direction (acattn_proj_problem.split_planes: forward image, then backward image)
+constexpr int SPLIT_SQ64 = 4 * 2 * 3 * 64;
+constexpr int PROJ_PLANES_DIR = 6 * SPLIT_SQ64;
+
 // acc += a . b over one K = 32 block with both operands split (a[p], b[q]: planes)
 __device__ __forceinline__ f4 mfma_split(const b8 (&a)[3], const b8 (&b)[3], f4 acc) {
 #define ACATTN_SPLIT_TERM(p, q) acc = mfma_bf(a[p], b[q], acc);

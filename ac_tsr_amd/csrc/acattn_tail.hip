@@ -623,6 +623,71 @@ __global__ void __launch_bounds__(256) tail_split_planes_kernel(const float* wd,
   for (int q = 0; q < 3; ++q) dst[((size_t)f * 3 + q) * 64 + lane] = p[q];
 }
 
+// The planes of SEVERAL layers in one launch (acattn_split_weights_many): per layer the tail planes above, bytewise, and
+// the projections' two images (acattn_proj.hip: [matrix][tile][s][plane][lane], 64 x 64 each, the gate's rows / columns
+// past G zero).  blockIdx.y = layer; blockIdx.x: 24 blocks for the twelve projection matrices, then the tail's matrices
+// (2 blocks per 64 x 64, I / 32 per I x 64).  One thread per 16-byte fragment as above.
+struct SplitManyArgs {
+  acattn_split_layer layer[ACATTN_SPLIT_MAX_LAYERS];
+};
+constexpr int SPLIT_MANY_PROJ_BLOCKS = 24, SPLIT_MANY_BLOCKS = SPLIT_MANY_PROJ_BLOCKS + 4 + 4 * (256 / 32);
+
+// fragment idx of the M x K plane matrix A[m][k] = T ? w[k][m] : w[m][k] (w row-major with `ld` columns; T: rows k >= nv
+// of w, else rows m >= nv, do not exist and read as zero)
+__device__ __forceinline__ void split_fragment(const float* w, b8* dst, int M, int K, int ld, int nv, bool T, int idx) {
+  const int KS = K / 32;
+  if (idx >= (M / 16) * KS * 64) return;
+  const int lane = idx & 63, f = idx >> 6, mt = f / KS, s = f % KS, c = lane & 15, g = lane >> 4, m = 16 * mt + c;
+  float x[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int k = tail_kperm(s, g, j);
+    const int row = T ? k : m, col = T ? m : k;
+    const float t = w[(size_t)min(row, nv - 1) * ld + col];
+    x[j] = row < nv ? t : 0.f;
+  }
+  b8 p[3];
+  split8(x, p[0], p[1], p[2]);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) dst[((size_t)f * 3 + q) * 64 + lane] = p[q];
+}
+
+__global__ void __launch_bounds__(256) split_many_kernel(const SplitManyArgs A) {
+  const acattn_split_layer& Ly = A.layer[blockIdx.y];
+  int b = blockIdx.x;
+  if (b < SPLIT_MANY_PROJ_BLOCKS) {
+    if (!Ly.proj_planes) return;
+    const int dir = b / 12, mi = (b % 12) >> 1, idx = (b & 1) * 256 + threadIdx.x;
+    // forward image: Wq, Waq, Wg, Wk, Wak, Wv; backward image: Waq, Wg, Wq, Wak, Wk, Wv
+    const float* w = dir == 0 ? (mi == 0 ? Ly.wq : mi == 1 ? Ly.waq : mi == 2 ? Ly.wg : mi == 3 ? Ly.wk : mi == 4 ? Ly.wak : Ly.wv)
+                              : (mi == 0 ? Ly.waq : mi == 1 ? Ly.wg : mi == 2 ? Ly.wq : mi == 3 ? Ly.wak : mi == 4 ? Ly.wk : Ly.wv);
+    const bool is_gate = mi == (dir == 0 ? 2 : 1);
+    if (!w) return;  // no gate: the slot is not written (and never read)
+    split_fragment(w, (b8*)Ly.proj_planes + (dir * 6 + mi) * SPLIT_SQ64, 64, 64, 64, is_gate ? Ly.G : 64, dir == 1, idx);
+    return;
+  }
+  if (!Ly.tail_planes) return;
+  b -= SPLIT_MANY_PROJ_BLOCKS;
+  const int I = Ly.I, RB = I / 32, SQ = SPLIT_SQ64, RECT = I * 64 * 3 / 8;
+  // Wd, W1, W2, Wd^T, W1^T, W2^T at the offsets of TailPlanes<I>
+  int mtx = 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const int nblk = k % 3 == 0 ? 2 : RB;
+    if (mtx == k && b >= nblk) {
+      b -= nblk;
+      ++mtx;
+    }
+  }
+  if (mtx >= 6) return;
+  const int which = mtx % 3;
+  const bool T = mtx >= 3;
+  const float* w = which == 0 ? Ly.wd : which == 1 ? Ly.w1 : Ly.w2;
+  const int M = which == 0 ? 64 : ((which == 1) != T ? I : 64), K = (which == 0 ? 64 * 64 : 64 * I) / M;
+  const int off = mtx == 0 ? 0 : mtx == 1 ? SQ : mtx == 2 ? SQ + RECT : mtx == 3 ? SQ + 2 * RECT : mtx == 4 ? 2 * SQ + 2 * RECT : 2 * SQ + 3 * RECT;
+  split_fragment(w, (b8*)Ly.tail_planes + off, M, K, T ? M : K, T ? K : M, T, b * 256 + threadIdx.x);
+}
+
 // the three planes of fragment (mt, s) of a plane matrix with KS K-blocks
 template <int KS>
 __device__ __forceinline__ void load_frag(const b8* mat, int mt, int s, int lane, b8 (&a)[3]) {
@@ -2118,6 +2183,15 @@ int acattn_launch_tail_split(const acattn_tail_problem& p, void* planes, hipStre
   if (p.H == 64 && p.I == 128) return launch_split_planes<128>(p, planes, stream);
   acattn_set_error("layer tail split planes: hidden 64, inner 256 or 128 only");
   return -1;
+}
+
+int acattn_launch_split_many(const acattn_split_layer* layers, int n_layers, hipStream_t stream) {
+  static_assert(TailPlanes<256>::SQ == SPLIT_SQ64 && TailPlanes<128>::BWD_2 == 2 * SPLIT_SQ64 + 3 * (128 * 64 * 3 / 8), "");
+  SplitManyArgs args;
+  memset(&args, 0, sizeof(args));
+  for (int k = 0; k < n_layers; ++k) args.layer[k] = layers[k];
+  hipLaunchKernelGGL(split_many_kernel, dim3(SPLIT_MANY_BLOCKS, n_layers), dim3(256), 0, stream, args);
+  return (int)hipGetLastError();
 }
 
 int acattn_select_tail_nb(int nb) {

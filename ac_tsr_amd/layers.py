@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import fused_ln, ops
+from . import planes as planes_mod
 from . import tail
 from .linear import projections, projections_qkv, skinny_linear
 from .ops import AttentionConfig, ExplicitRandomness, StructuredMask
@@ -172,21 +173,24 @@ class AttackRTransformerLayer(nn.Module):
                                adversarial=self.adversarial, anneal_rate=rate)
 
     def forward(self, hidden_states, attention_mask, return_attention_prob=False, return_all_attention_prob=False,
-                _rnd=None, _need_attacked=True, _attack_upstream=True, _rows=None):
+                _rnd=None, _need_attacked=True, _attack_upstream=True, _rows=None, _planes=None):
         """`_need_attacked=False` (set by the encoder for layers whose attacked output nobody can observe) skips the
         dense / LayerNorm / feed-forward tail of the attacked branch and returns None in its place.
         `_rows` ([B, R] positions) makes the layer return only those positions of its two outputs ([B, R, H]): the tail
         is position-wise, so it then runs on the selected rows alone (the models read one position per sequence of the
-        last layer, abstract_recommender.py:130-134; AcBERT4Rec the masked positions, acbert4rec.py:219-225)."""
+        last layer, abstract_recommender.py:130-134; AcBERT4Rec the masked positions, acbert4rec.py:219-225).
+        `_planes` (planes.LayerPlanes): the split weight planes of this layer the encoder made for this forward; a layer
+        called without them splits its weights where it uses them."""
         att = self.attack_attention
         cal = att.calibrator_params()
         if not self.adversarial:
             return self._forward_spatial_only(hidden_states, attention_mask, return_attention_prob, return_all_attention_prob,
-                                              _rnd, _rows)
+                                              _rnd, _rows, _planes)
         mq, mk, mv, qa, ka, gate_logits, hidden_res, extras = projections(
             hidden_states, att.query, att.key, att.value, att.attack_query_transform, att.attack_key_transform,
             self.gate if self.combine_option == 'gate' else None, attack_upstream=_attack_upstream,
-            spatial=(cal.get("w_order"), cal.get("b_order"), cal.get("w_dist"), cal.get("b_dist"), att.num_attention_heads))
+            spatial=(cal.get("w_order"), cal.get("b_order"), cal.get("w_dist"), cal.get("b_dist"), att.num_attention_heads),
+            planes=_planes)
         cfg = self._config()
         core_rnd = None
         if _rnd is not None:
@@ -216,10 +220,11 @@ class AttackRTransformerLayer(nn.Module):
             if one_launch and _rows is not None:
                 # the fused tail picks the rows itself: no gather launches in front of it, no scatter launches behind
                 return tail.layer_tail(ctx_layer, hidden_res, att, self.feed_forward, pick(keep_out), pick(keep_ffn),
-                                       pick=_rows)
+                                       pick=_rows, planes=_planes)
             ctx_layer, keep_out, keep_ffn = pick(ctx_layer), pick(keep_out), pick(keep_ffn)
             if fused:
-                return tail.layer_tail(ctx_layer, residual, att, self.feed_forward, keep_out, keep_ffn)
+                return tail.layer_tail(ctx_layer, residual, att, self.feed_forward, keep_out, keep_ffn,
+                                       planes=_planes if one_launch else None)
             return self.feed_forward(att.output(ctx_layer, residual, keep_out), keep_ffn)
 
         attacked_feedforward_output = None
@@ -241,7 +246,8 @@ class AttackRTransformerLayer(nn.Module):
                     all_attention_prob)
         return attacked_feedforward_output, calibrated_feedforward_output, attack_mask, combined_attention_prob
 
-    def _forward_spatial_only(self, hidden_states, attention_mask, return_attention_prob, return_all_attention_prob, _rnd, _rows):
+    def _forward_spatial_only(self, hidden_states, attention_mask, return_attention_prob, return_all_attention_prob, _rnd, _rows,
+                              _planes=None):
         """The layer without the adversarial calibrator: three projections, the spatial-only attention core, ONE tail.
         Returns (None, calibrated_feedforward_output, None, None)."""
         if return_attention_prob or return_all_attention_prob:
@@ -268,11 +274,13 @@ class AttackRTransformerLayer(nn.Module):
             index = _rows.unsqueeze(-1).expand(-1, -1, hidden_states.shape[-1])
             pick = lambda t: None if t is None else t.gather(1, index)
             if one_launch:  # the fused tail picks the rows itself
-                out = tail.layer_tail(ctx_cal, hidden_res, att, self.feed_forward, pick(keep_out), pick(keep_ffn), pick=_rows)
+                out = tail.layer_tail(ctx_cal, hidden_res, att, self.feed_forward, pick(keep_out), pick(keep_ffn), pick=_rows,
+                                      planes=_planes)
                 return None, out, None, None
             ctx_cal, hidden_res, keep_out, keep_ffn = pick(ctx_cal), pick(hidden_res), pick(keep_out), pick(keep_ffn)
         if one_launch or (can_tail and torch.is_grad_enabled()):
-            out = tail.layer_tail(ctx_cal, hidden_res, att, self.feed_forward, keep_out, keep_ffn)
+            out = tail.layer_tail(ctx_cal, hidden_res, att, self.feed_forward, keep_out, keep_ffn,
+                                  planes=_planes if one_launch else None)
         else:
             out = self.feed_forward(att.output(ctx_cal, hidden_res, keep_out), keep_ffn)
         return None, out, None, None
@@ -307,6 +315,9 @@ class AttackRTransformerEncoder(nn.Module):
         all_attack_masks = []
         all_attention_prob = [] if return_attention_prob else None
         all_probs = [] if return_all_attention_prob else None
+        # hidden 64 on split products: the weights of every layer split into bf16 planes by ONE launch, here; the layers'
+        # projections and tails (and their backward launches) read them (planes.py; None where that does not apply)
+        layer_planes = planes_mod.make(list(self.layer), hidden_states, _last_rows)
         for layer_idx, layer_module in enumerate(self.layer):
             rnd = _rnds[layer_idx] if _rnds is not None else None
             # only the calibrated output feeds the next layer (layers.py:1112): with output_all_encoded_layers=False the
@@ -316,7 +327,8 @@ class AttackRTransformerEncoder(nn.Module):
                                 _rnd=rnd, _need_attacked=need_attacked,
                                 # the first layer owes no input gradient to an attack transform
                                 _attack_upstream=layer_idx > 0 or not state_of(self).prune_dead_work,
-                                _rows=_last_rows if layer_idx == len(self.layer) - 1 else None)
+                                _rows=_last_rows if layer_idx == len(self.layer) - 1 else None,
+                                _planes=layer_planes[layer_idx])
             attacked_hidden_states, calibrated_hidden_states, attack_mask, combined_attention_prob = outs[:4]
             hidden_states = calibrated_hidden_states  # layers.py:1112
             all_attack_masks.append(attack_mask)

@@ -163,8 +163,11 @@ class _FusedProjections(torch.autograd.Function):
         return p
 
     @staticmethod
-    def forward(ctx, x, wq, bq, wk, bk, wv, bv, waq, baq, wak, bak, wg, bg, attack_upstream, state, spatial=None):
-        """`spatial` = (w_order, b_order, w_dist, b_dist, n_heads) or None.  With it (and a [B, L, H] input) the launch
+    def forward(ctx, x, wq, bq, wk, bk, wv, bv, waq, baq, wak, bak, wg, bg, attack_upstream, state, spatial=None,
+                planes=None):
+        """`planes` (planes.LayerPlanes or None): the split weight planes the encoder made for this forward; both launches
+        of the node then read their weight fragments from them instead of splitting the weights in every workgroup.
+        `spatial` = (w_order, b_order, w_dist, b_dist, n_heads) or None.  With it (and a [B, L, H] input) the launch
         also writes what the attention core would otherwise re-derive per head / per query block: the rank-1 halves of
         the two spatial affines (acattn_problem.affine) and sigmoid(gate) in place of the gate logits
         (acattn_problem.gate_is_prob).  The gate output then HOLDS PROBABILITIES while the gradient that comes back for
@@ -191,6 +194,9 @@ class _FusedProjections(torch.autograd.Function):
             p.n_heads, p.L = n_heads, L
             out.affine = _ptr(affine)
             out.gate_prob = 1 if gate is not None else 0
+        ctx.planes = planes if (planes is not None and planes.proj is not None) else None
+        if ctx.planes is not None:
+            p.split_planes = _ptr(ctx.planes.proj)
         _lib.check(_lib.load().acattn_projections_fwd(C.byref(p), C.byref(out), _stream()), "projections_fwd")
         ctx.save_for_backward(x, mq, mk, *(t if t is not None else x.new_empty(0) for t in params))
         ctx.has_gate = wg is not None
@@ -233,6 +239,8 @@ class _FusedProjections(torch.autograd.Function):
             dx = torch.empty_like(x) if need_dx else None
             io.dmq_total, io.dmk_total, io.dx = _ptr(dmq_t), _ptr(dmk_t), _ptr(dx)
             p = _FusedProjections._problem(x, *params)
+            if ctx.planes is not None:  # the forward's planes: made from these weights, alive as long as this node
+                p.split_planes = _ptr(ctx.planes.proj)
             ws_bytes = int(_lib.load().acattn_projections_bwd_workspace_bytes(C.byref(p)))
             ws = torch.empty(ws_bytes // 4, device=x.device, dtype=torch.float32) if ws_bytes > 0 else None
             io.workspace = _ptr(ws)  # transposed weight copies at hidden 128 / 256
@@ -254,7 +262,7 @@ class _FusedProjections(torch.autograd.Function):
         if jobs:
             for (slot, _, _, _), (gw, gb) in zip(jobs, linear_wgrad_grouped([(i, g, wb) for _, i, g, wb in jobs], ctx.state)):
                 grads[slot - 1], grads[slot] = gw, gb
-        return (dx, *grads, None, None, None)
+        return (dx, *grads, None, None, None, None)
 
 
 def _affine_workspace(state, device, B, n_heads, L):
@@ -274,13 +282,14 @@ def _affine_workspace(state, device, B, n_heads, L):
     return ws
 
 
-def projections(x, query, key, value, attack_query, attack_key, gate=None, attack_upstream=True, spatial=None):
+def projections(x, query, key, value, attack_query, attack_key, gate=None, attack_upstream=True, spatial=None, planes=None):
     """(mq, mk, mv, qa, ka, gate_logits or None, x_res, extras) of one encoder layer; see _Projections.
     `attack_upstream=False` tells the node that nothing that produced `x` holds attack transforms (the first encoder
     layer).  `x_res` is `x` for the residual connections of the layer (see _FusedProjections.forward; plain `x` on the
     other paths).  `spatial` = (w_order, b_order, w_dist, b_dist, n_heads): the single-launch path then also produces
     the affine planes and hands the gate over as probabilities; `extras` = {'affine': tensor, 'gate_is_prob': bool}
-    says what it did (empty on the other paths) and goes to ops.calibrated_attention as keyword arguments."""
+    says what it did (empty on the other paths) and goes to ops.calibrated_attention as keyword arguments.
+    `planes` (planes.LayerPlanes or None): this forward's split weight planes of the layer, for the single-launch path."""
     node = _Projections if torch.is_grad_enabled() else None
     if x.is_cuda and FUSED_PROJECTIONS and x.dtype == torch.float32 and all(
             m.bias is not None for m in (query, key, value, attack_query, attack_key) + ((gate,) if gate is not None else ())):
@@ -297,7 +306,7 @@ def projections(x, query, key, value, attack_query, attack_key, gate=None, attac
     if node is _FusedProjections:
         if not PRODUCER_EXTRAS or (spatial is not None and any(t is None for t in spatial[:4])):
             spatial = None
-        *out, affine = node.apply(*args, spatial)
+        *out, affine = node.apply(*args, spatial, planes)
         extras = {} if affine is None else {"affine": affine, "gate_is_prob": gate is not None}
         return (*out, extras)
     out = node.apply(*args)

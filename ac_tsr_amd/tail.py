@@ -5,7 +5,8 @@
 
 `_FusedLayerTail` (hidden 64, inner 256 / 128: the shipped configuration): ONE HIP launch forward
 (acattn_layer_tail_fwd: the three products with the chain held in registers, csrc/acattn_tail.hip; at hidden 64 on bf16
-matrix instructions with exactly split operands, the weights split once per node by acattn_layer_tail_split_weights)
+matrix instructions with exactly split operands, the weights split once per encoder forward (planes.py) or, for a node
+called on its own, once per node by acattn_layer_tail_split_weights)
 and, backward, one launch for every input gradient and the LayerNorm partials (acattn_layer_tail_bwd) + the grouped
 weight-gradient launch pair + one reduction of the partials.
 
@@ -51,9 +52,10 @@ def _tail_problem(c, x, wd, bd, g1, b1, w1, bb1, w2, bb2, g2, b2, eps1, eps2, p1
 class _FusedLayerTail(torch.autograd.Function):
     @staticmethod
     def forward(ctx, c, x, wd, bd, g1, b1, w1, bb1, w2, bb2, g2, b2, eps1, eps2, p1, p2, keep1, keep2, seed1, seed2,
-                seed_tensor, state, pick=None):
+                seed_tensor, state, pick=None, shared=None):
         """`pick` ([B, R] int64 positions): the tail runs on those positions of c / x ([B, L, H]) only and returns
-        [B, R, H]; explicit keep masks are then [B, R, H] as well."""
+        [B, R, H]; explicit keep masks are then [B, R, H] as well.  `shared` (planes.LayerPlanes or None): the weight
+        planes the encoder made for this forward; without them the node splits the weights itself."""
         ctx.state = state
         c, x = c.contiguous(), x.contiguous()
         params = tuple(t.contiguous() for t in (wd, bd, g1, b1, w1, bb1, w2, bb2, g2, b2))
@@ -80,7 +82,11 @@ class _FusedLayerTail(torch.autograd.Function):
         # from the weights of THIS call and die with the node, so an in-place update (Adam) can never leave them stale
         planes = None
         nbytes = int(lib.acattn_layer_tail_split_bytes(H, I, rows))
-        if nbytes > 0:
+        ctx.shared = None
+        if nbytes > 0 and shared is not None and shared.tail is not None and shared.tail.numel() * 4 == nbytes:
+            ctx.shared = shared  # made at the head of this encoder forward from these weights; kept for the backward
+            p.split_planes = _ptr(shared.tail)
+        elif nbytes > 0:
             planes = new(nbytes // 4)
             _lib.check(lib.acattn_layer_tail_split_weights(C.byref(p), _ptr(planes), _stream()), "layer_tail_split_weights")
             p.split_planes = _ptr(planes)
@@ -113,6 +119,8 @@ class _FusedLayerTail(torch.autograd.Function):
         d_out = d_out.contiguous()
         p = _tail_problem(c, x, *params, eps1, eps2, p1, p2, k1, k2, seed1, seed2, seed_t, pick)
         p.split_planes = _ptr(planes) if planes.numel() else None  # the forward's planes: the same products both ways
+        if ctx.shared is not None:
+            p.split_planes = _ptr(ctx.shared.tail)
         sv = _lib.TailSaved()
         sv.h1, sv.st1, sv.a, sv.act, sv.h3, sv.st2 = (_ptr(t) for t in (h1, st1, a, act, h3, st2))
         sv.gelu_grad = _ptr(dgelu) if dgelu.numel() else None
@@ -143,7 +151,7 @@ class _FusedLayerTail(torch.autograd.Function):
             gb = ops.sum_rows0(part, ctx.state).view(4, H)  # (dgamma1, dbeta1, dgamma2, dbeta2)
             grads = [gwd, gbd, gb[0], gb[1], gw1, gb1, gw2, gb2, gb[2], gb[3]]
             ctx.state.watch(gb, grads[2], grads[3], grads[8], grads[9])
-        return (d_c, d_x, *grads, None, None, None, None, None, None, None, None, None, None, None)
+        return (d_c, d_x, *grads, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
 
@@ -210,10 +218,11 @@ def fused_supported(att, ffn) -> bool:
     return FUSED_KERNEL and bool(_lib.load().acattn_layer_tail_supported(H, ffn.dense_1.out_features))
 
 
-def layer_tail(ctx_layer, input_tensor, att, ffn, keep_out=None, keep_ffn=None, pick=None):
+def layer_tail(ctx_layer, input_tensor, att, ffn, keep_out=None, keep_ffn=None, pick=None, planes=None):
     """FeedForward(attention_output(ctx_layer, input_tensor)) for one branch; `att` is the AttackRMultiHeadAttention
     (dense, LayerNorm, out_dropout), `ffn` the FeedForward module.  keep_* feed explicit dropout masks (parity).
-    `pick` ([B, R] positions; fused node only): run on those positions of the two [B, L, H] inputs, return [B, R, H]."""
+    `pick` ([B, R] positions; fused node only): run on those positions of the two [B, L, H] inputs, return [B, R, H].
+    `planes` (planes.LayerPlanes or None; fused node only): this forward's weight planes of the layer."""
     training = att.training
     p1 = att.out_dropout.p if (training or keep_out is not None) else 0.0
     p2 = ffn.dropout.p if (training or keep_ffn is not None) else 0.0
@@ -224,7 +233,7 @@ def layer_tail(ctx_layer, input_tensor, att, ffn, keep_out=None, keep_ffn=None, 
     extra = ()
     node = _LayerTail
     if fused_supported(att, ffn):
-        node, extra = _FusedLayerTail, (pick,)
+        node, extra = _FusedLayerTail, (pick, planes)
     else:
         assert pick is None, "row selection inside the tail needs the fused node"
     return node.apply(ctx_layer, input_tensor, att.dense.weight, att.dense.bias, att.LayerNorm.weight,

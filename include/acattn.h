@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ACATTN_ABI_VERSION 32
+#define ACATTN_ABI_VERSION 33
 
 /* attention-mask encodings (recbole/model/abstract_recommender.py:136-143 builds the dense form) */
 enum {
@@ -498,6 +498,32 @@ int64_t acattn_layer_tail_split_bytes(int32_t H, int32_t I, int32_t rows);
 /* ABI 31: writes the planes of p->wd, p->w1, p->w2 (hidden 64) into `planes` (one launch on `stream`). */
 int acattn_layer_tail_split_weights(const acattn_tail_problem* p, void* planes, void* stream);
 
+/* ABI 33: the split planes of SEVERAL layers in ONE launch -- what an encoder forward needs of them, written once at its
+ * head instead of once per autograd node (tails) and once per workgroup of every launch (projections).  Per layer either
+ * half may be left out (its planes pointer NULL):
+ *   tail_planes  acattn_tail_problem.split_planes of wd / w1 / w2 ([64,64], [I,64], [64,I], I = 256 or 128), bytewise what
+ *                acattn_layer_tail_split_weights writes;
+ *   proj_planes  acattn_proj_problem.split_planes of wq, wk, wv, waq, wak ([64,64]) and wg ([G,64], G <= 64, or NULL without
+ *                the gate: its two slots are then left unwritten).  16-byte fragments [matrix][tile][K-block][plane][lane];
+ *                forward image (A[m][k] = W[m][k]) in the order Wq, Waq, Wg, Wk, Wak, Wv, then the backward image
+ *                (A[m][k] = W[k][m]) in the order Waq, Wg, Wq, Wak, Wk, Wv; gate rows / columns past G are zeros.
+ * All planes pointers 16-byte aligned.  `layers` is a host array read during the call; at most ACATTN_SPLIT_MAX_LAYERS
+ * entries per call. */
+#define ACATTN_SPLIT_MAX_LAYERS 8
+typedef struct acattn_split_layer {
+  const float *wd, *w1, *w2;
+  int32_t I;
+  void* tail_planes;
+  const float *wq, *wk, *wv, *waq, *wak, *wg;
+  int32_t G;
+  void* proj_planes;
+} acattn_split_layer;
+int acattn_split_weights_many(const acattn_split_layer* layers, int32_t n_layers, void* stream);
+/* ABI 33: bytes of acattn_proj_problem.split_planes, or 0 where the projections do not run on split products: hidden other
+ * than 64, a gate wider than 64, acattn_linear_products(ACATTN_LINEAR_PRODUCTS_FP32).  The answer may change with that
+ * setting: ask before each forward. */
+int64_t acattn_projections_split_bytes(int32_t H, int32_t G);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * The six projections in front of the attention core in one launch (forward) / one launch (input gradients):
  *     mq, mk, mv = query(x), key(x), value(x)                               recbole/model/layers.py:687-689
@@ -517,6 +543,15 @@ typedef struct acattn_proj_problem {
    * head count and the sequence length (rows = B * L, row r sits at position r % L of sequence r / L) */
   const float *w_order, *b_order, *w_dist, *b_dist; /* [2*dh], [1], [2*dh], [1] */
   int32_t n_heads, L;
+  /* ABI 33, optional: hidden 64 with a gate of at most 64 outputs only, the weight planes acattn_split_weights_many wrote
+   * from THESE six weights (acattn_projections_split_bytes(H, G) bytes, 16-byte aligned: the forward image, then the
+   * transposed image of the backward).  Given, acattn_projections_fwd / _bwd read their weight fragments from the planes
+   * (proj_planes_fwd_kernel / proj_planes_bwd_kernel: one wave per workgroup, no LDS image, no split of the weights inside
+   * the launch); the products and every tensor written are bitwise those of the NULL form, which splits the weights
+   * inside every workgroup.  The planes are a copy of the weights: after any change of a weight they must be written again
+   * before use.  Planes given where these kernels do not run (acattn_linear_products(0) since they were made) are not read:
+   * the launch takes the kernels it would take without them.  acattn_projections_qkv_fwd does not read the field. */
+  const void* split_planes;
 } acattn_proj_problem;
 
 typedef struct acattn_proj_out {
