@@ -15,7 +15,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("ACATTN_LIB") or os.path.join(CSRC, "libacattn.so")  # ACATTN_LIB: experiments only
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "acattn.h")
 
-ABI_VERSION = 33
+ABI_VERSION = 34
 MAX_MASKS = 8  # ACATTN_MAX_MASKS
 NSTAT = 8
 MASK_STRUCTURED, MASK_DENSE_LL, MASK_DENSE_L = 0, 1, 2
@@ -163,6 +163,8 @@ SYMBOLS = {
     "acattn_full_sort_ce_fwd": (C.c_int, [C.POINTER(CeProblem), _f, _f, _f, C.c_void_p]),
     "acattn_full_sort_ce_fwd_dir": (C.c_int, [C.POINTER(CeProblem), _f, _f, _f, _f, C.c_void_p]),
     "acattn_full_sort_ce_bwd": (C.c_int, [C.POINTER(CeProblem), _f, _f, _f, _f, _f, C.c_void_p]),
+    "acattn_full_sort_ce_fwd_pair_workspace_bytes": (C.c_int64, [C.POINTER(CeProblem), C.POINTER(CeProblem)]),
+    "acattn_full_sort_ce_fwd_pair": (C.c_int, [C.POINTER(CeProblem), C.POINTER(CeProblem), _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "acattn_full_sort_ce_products": (C.c_int, [C.c_int]),
     "acattn_linear_products": (C.c_int, [C.c_int]),
     "acattn_dropout_add_layernorm_fwd": (C.c_int, [C.POINTER(LnProblem), _f, _f, C.c_void_p]),
@@ -204,6 +206,8 @@ SYMBOLS = {
     "acattn_mask_penalty_rows": (C.c_int, [_f, C.c_int32, C.c_int32, C.c_int32, _f, C.c_void_p]),
     "acattn_attacked_loss_finish_rows": (C.c_int, [_f, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, _f, _f, C.c_int32,
                                                   C.c_void_p]),
+    "acattn_attacked_loss_finish_rows_pair": (C.c_int, [_f, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, _f, _f,
+                                                       C.c_int32, _f, C.c_int32, _f, C.c_void_p]),
     "acattn_mask_penalty_drows": (C.c_int, [_f, _f, C.c_float, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "acattn_mask_penalty_drows_dir": (C.c_int, [_f, _f, C.c_float, C.c_int32, C.c_void_p, C.c_int32, _f, _f, C.c_int32, C.c_void_p]),
     "acattn_mask_penalty_bwd_scaled": (C.c_int, [_f, _f, _f, C.c_float, C.c_int64, _f, C.c_void_p]),

@@ -7,6 +7,7 @@ forward and backward each sweep the item table once on the matrix cores.  No CPU
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
@@ -15,12 +16,63 @@ from .state import DEFAULT as _DEFAULT_STATE
 from .ops import _need_cuda, _ptr, _stream
 
 
+# Both losses of a training step from one forward sweep of the catalogue (acattn_full_sort_ce_fwd_pair) where that
+# applies; ACATTN_CE_PAIRED=0 keeps the two separate sweeps (A/B runs, tests).
+PAIRED_FORWARD = os.environ.get("ACATTN_CE_PAIRED", "1") != "0"
+
+
 def _problem(out, table, target) -> _lib.CeProblem:
     B, H = out.shape
     p = _lib.CeProblem()
     p.B, p.N, p.H = B, table.shape[0], H
     p.out, p.table, p.target = _ptr(out), _ptr(table), _ptr(target)
     return p
+
+
+class PairedCE:
+    """What paired_forward() computed for the two loss nodes: set a = the attacked rows (loss and direction, as
+    acattn_full_sort_ce_fwd_dir), set c = the calibrated rows (loss, as acattn_full_sort_ce_fwd).  `mean_c` is written by
+    the attacked node's finishing launch, which therefore has to run before the calibrated node reads it."""
+    __slots__ = ("lse_a", "row_loss_a", "direction", "lse_c", "row_loss_c", "mean_c", "mean_written")
+
+    def __init__(self, lse_a, row_loss_a, direction, lse_c, row_loss_c, mean_c):
+        self.lse_a, self.row_loss_a, self.direction = lse_a, row_loss_a, direction
+        self.lse_c, self.row_loss_c, self.mean_c = lse_c, row_loss_c, mean_c
+        self.mean_written = False
+
+
+def paired_forward(out_a: torch.Tensor, out_c: torch.Tensor, table: torch.Tensor, target: torch.Tensor):
+    """The forward sweeps of _AttackedLossRows (rows out_a) and _FullSortCEMean (rows out_c) as ONE sweep of the table, not
+    recorded by autograd: row split, sweep and finish for both row sets in three launches.  Returns a PairedCE for the two
+    nodes' forwards, or None where the paired form does not apply (switch off, or the library answers -100: hidden size
+    other than 64, exact-fp32 products, a small catalogue in the default mode, too many rows) -- the nodes then run their
+    own sweeps."""
+    if not PAIRED_FORWARD or out_a.shape[1] != 64 or out_a.shape[1:] != out_c.shape[1:]:
+        return None
+    for name, t in (("attacked output", out_a), ("calibrated output", out_c), ("item table", table)):
+        _need_cuda(name, t)
+    _need_cuda("target", target, torch.int64)
+    with torch.no_grad():
+        lib = _lib.load()
+        out_a, out_c = out_a.detach().contiguous(), out_c.detach().contiguous()
+        pa, pc = _problem(out_a, table, target), _problem(out_c, table, target)
+        nbytes = lib.acattn_full_sort_ce_fwd_pair_workspace_bytes(C.byref(pa), C.byref(pc))
+        if nbytes == -100:
+            return None
+        if nbytes < 0:
+            _lib.check(int(nbytes), "full_sort_ce_fwd_pair_workspace_bytes")
+        dev = out_a.device
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        lse_a = torch.empty(out_a.shape[0], device=dev, dtype=torch.float32)
+        lse_c = torch.empty(out_c.shape[0], device=dev, dtype=torch.float32)
+        row_loss_a, row_loss_c = torch.empty_like(lse_a), torch.empty_like(lse_c)
+        direction = torch.empty_like(out_a)
+        rc = lib.acattn_full_sort_ce_fwd_pair(C.byref(pa), C.byref(pc), _ptr(ws), _ptr(lse_a), _ptr(row_loss_a), _ptr(direction),
+                                              _ptr(lse_c), _ptr(row_loss_c), _stream())
+        if rc == -100:
+            return None
+        _lib.check(rc, "full_sort_ce_fwd_pair")
+        return PairedCE(lse_a, row_loss_a, direction, lse_c, row_loss_c, torch.empty((), device=dev, dtype=torch.float32))
 
 
 class _FullSortCE(torch.autograd.Function):
@@ -122,9 +174,19 @@ class _FullSortCEMean(torch.autograd.Function):
     launches."""
 
     @staticmethod
-    def forward(ctx, out, table, target, state):
-        row_loss = _FullSortCE.forward(ctx, out, table, target, state)
-        return row_loss.mean()
+    def forward(ctx, out, table, target, state, pair=None):
+        if pair is None:
+            row_loss = _FullSortCE.forward(ctx, out, table, target, state)
+            return row_loss.mean()
+        # the paired forward swept these rows already and the attacked node's finish wrote their mean
+        if not pair.mean_written or pair.lse_c.shape[0] != out.shape[0]:
+            raise _lib.AcattnError("paired cross-entropy: the attacked loss node has to run first (its finishing launch "
+                                   "writes the calibrated rows' mean), on a record made for these rows")
+        ctx.state = state
+        ctx.save_for_backward(out, table, target, pair.lse_c)
+        ctx.ws_bytes = _lib.load().acattn_full_sort_ce_workspace_bytes(C.byref(_problem(out, table, target)))
+        ctx.tick = state.next_tick()
+        return pair.mean_c
 
     @staticmethod
     def backward(ctx, d_loss):
@@ -141,7 +203,7 @@ class _FullSortCEMean(torch.autograd.Function):
         _lib.check(lib.acattn_full_sort_ce_bwd(C.byref(p), _ptr(lse), _ptr(d_loss.contiguous()), _ptr(ws), _ptr(d_out),
                                                _ptr(d_table), _stream()), "full_sort_ce_bwd")
         ctx.state.publish_table_grad(getattr(ctx, "tick", -1), table, d_table)  # (see StepState.table_grad)
-        return d_out, d_table, None, None
+        return d_out, d_table, None, None, None
 
 
 class _AttackedLoss(torch.autograd.Function):
@@ -236,28 +298,38 @@ class _AttackedLossRows(torch.autograd.Function):
     d M = 2 d_pen (M - 1) from the tile they rebuild (acattn_bwd_io.d_penalty_part)."""
 
     @staticmethod
-    def forward(ctx, out, table, target, weight, state, *pens):
+    def forward(ctx, out, table, target, weight, state, pair, *pens):
         ctx.state = state
         lib = _lib.load()
         B = out.shape[0]
         p = _problem(out, table, target)
         nbytes = lib.acattn_full_sort_ce_workspace_bytes(C.byref(p))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
-        lse = torch.empty(B, device=out.device, dtype=torch.float32)
-        row_loss = torch.empty_like(lse)
-        direction = torch.empty_like(out)
-        rc = lib.acattn_full_sort_ce_fwd_dir(C.byref(p), _ptr(ws), _ptr(lse), _ptr(row_loss), _ptr(direction), _stream())
-        if rc == -100:  # too many rows for the per-workgroup slabs: plain forward, regular backward sweep
-            direction = None
-            _lib.check(lib.acattn_full_sort_ce_fwd(C.byref(p), _ptr(ws), _ptr(lse), _ptr(row_loss), _stream()), "full_sort_ce_fwd")
-        else:
-            _lib.check(rc, "full_sort_ce_fwd_dir")
         pens = tuple(t.contiguous() for t in pens)
         ptrs = (C.c_void_p * len(pens))(*(t.data_ptr() for t in pens))
         res = torch.empty(2 + len(pens), device=out.device, dtype=torch.float32)
-        _lib.check(lib.acattn_attacked_loss_finish_rows(_ptr(row_loss), B, ptrs, len(pens), pens[0].numel(), weight, _ptr(res),
-                                                        _ptr(direction), 0 if direction is None else direction.numel(),
-                                                        _stream()), "attacked_loss_finish_rows")
+        if pair is not None:  # paired_forward() swept these rows; the finish also averages the calibrated rows' losses
+            if pair.lse_a.shape[0] != B:
+                raise _lib.AcattnError("paired cross-entropy: the record was made for another row set")
+            lse, row_loss, direction = pair.lse_a, pair.row_loss_a, pair.direction
+            _lib.check(lib.acattn_attacked_loss_finish_rows_pair(_ptr(row_loss), B, ptrs, len(pens), pens[0].numel(), weight,
+                                                                 _ptr(res), _ptr(direction), direction.numel(),
+                                                                 _ptr(pair.row_loss_c), pair.row_loss_c.shape[0], _ptr(pair.mean_c),
+                                                                 _stream()), "attacked_loss_finish_rows_pair")
+            pair.mean_written = True
+        else:
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
+            lse = torch.empty(B, device=out.device, dtype=torch.float32)
+            row_loss = torch.empty_like(lse)
+            direction = torch.empty_like(out)
+            rc = lib.acattn_full_sort_ce_fwd_dir(C.byref(p), _ptr(ws), _ptr(lse), _ptr(row_loss), _ptr(direction), _stream())
+            if rc == -100:  # too many rows for the per-workgroup slabs: plain forward, regular backward sweep
+                direction = None
+                _lib.check(lib.acattn_full_sort_ce_fwd(C.byref(p), _ptr(ws), _ptr(lse), _ptr(row_loss), _stream()), "full_sort_ce_fwd")
+            else:
+                _lib.check(rc, "full_sort_ce_fwd_dir")
+            _lib.check(lib.acattn_attacked_loss_finish_rows(_ptr(row_loss), B, ptrs, len(pens), pens[0].numel(), weight, _ptr(res),
+                                                            _ptr(direction), 0 if direction is None else direction.numel(),
+                                                            _stream()), "attacked_loss_finish_rows")
         ctx.has_dir = direction is not None
         ctx.save_for_backward(out, table, target, lse, direction if direction is not None else lse, res)
         ctx.weight, ctx.ws_bytes, ctx.pen_shapes = weight, nbytes, [t.shape for t in pens]
@@ -293,24 +365,58 @@ class _AttackedLossRows(torch.autograd.Function):
         else:
             _lib.check(lib.acattn_mask_penalty_drows(_ptr(res[2:]), _ptr(d_loss), ctx.weight / n, count, dp, n, _stream()),
                        "mask_penalty_drows")
-        d_pens = [d_flat[l].view(ctx.pen_shapes[l]) if ctx.needs_input_grad[5 + l] else None for l in range(n)]
-        return (d_out, d_table, None, None, None, *d_pens)
+        d_pens = [d_flat[l].view(ctx.pen_shapes[l]) if ctx.needs_input_grad[6 + l] else None for l in range(n)]
+        return (d_out, d_table, None, None, None, None, *d_pens)
+
+
+def _penalty_rows_of(masks):
+    """The attention nodes' penalty row sums of `masks` where _AttackedLossRows applies, else None."""
+    from . import ops
+    pens = [getattr(m, "_acattn_pen", None) for m in masks]
+    if (ops.PENALTY_ROWS and len(masks) <= _lib.MAX_MASKS and all(t is not None and t.is_cuda for t in pens)
+            and all(t.shape == pens[0].shape for t in pens)):
+        return pens
+    return None
+
+
+def _fusable_masks(masks):
+    masks = [m for m in masks if m is not None]
+    if not masks or any(m.numel() != masks[0].numel() or m.dtype != torch.float32 or not m.is_cuda for m in masks):
+        return None
+    return masks
 
 
 def attacked_loss(output: torch.Tensor, table: torch.Tensor, target: torch.Tensor, masks, weight: float,
                   state=_DEFAULT_STATE):
     """-CE(output @ table^T, target) + weight * mean_l ||1 - M_l||_2 (acsasrec.py:129-137) as one autograd node, or None
     when the fused form does not apply (no mask, masks of different sizes)."""
-    masks = [m for m in masks if m is not None]
-    if not masks or any(m.numel() != masks[0].numel() or m.dtype != torch.float32 or not m.is_cuda for m in masks):
+    masks = _fusable_masks(masks)
+    if masks is None:
         return None
     _need_cuda("target", target, torch.int64)
-    from . import ops
-    pens = [getattr(m, "_acattn_pen", None) for m in masks]
-    if (ops.PENALTY_ROWS and len(masks) <= _lib.MAX_MASKS and all(t is not None and t.is_cuda for t in pens)
-            and all(t.shape == pens[0].shape for t in pens)):
-        return _AttackedLossRows.apply(output.contiguous(), table, target, float(weight), state, *pens)
+    pens = _penalty_rows_of(masks)
+    if pens is not None:
+        return _AttackedLossRows.apply(output.contiguous(), table, target, float(weight), state, None, *pens)
     return _AttackedLoss.apply(output.contiguous(), table, target, float(weight), state, *masks)
+
+
+def paired_losses(attacked_output: torch.Tensor, calibrated_output: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
+                  masks, weight: float, state=_DEFAULT_STATE):
+    """Both losses of a training step, (attacked_loss(attacked_output, ...), full_sort_cross_entropy(calibrated_output,
+    ...)), from ONE forward sweep of the catalogue (paired_forward), as the same two autograd nodes the separate calls
+    build.  None where that does not apply -- no fused attacked loss on penalty row sums, or no paired forward -- and the
+    caller makes the two calls."""
+    masks = _fusable_masks(masks)
+    pens = None if masks is None else _penalty_rows_of(masks)
+    if pens is None:
+        return None
+    pair = paired_forward(attacked_output, calibrated_output, table, target)
+    if pair is None:
+        return None
+    # (this order: the attacked node's finishing launch also writes the calibrated rows' mean)
+    att = _AttackedLossRows.apply(attacked_output.contiguous(), table, target, float(weight), state, pair, *pens)
+    cal = _FullSortCEMean.apply(calibrated_output.contiguous(), table, target, state, pair)
+    return att, cal
 
 
 def full_sort_cross_entropy(output: torch.Tensor, table: torch.Tensor, target: torch.Tensor,
@@ -318,7 +424,7 @@ def full_sort_cross_entropy(output: torch.Tensor, table: torch.Tensor, target: t
     """mean_b [ logsumexp_n(output_b . table_n) - output_b . table_target(b) ].  `table_grad=False` declares that the
     table's gradient of this loss will not be taken (see _FullSortCEDir): same values, cheaper backward."""
     if table_grad:
-        return _FullSortCEMean.apply(output.contiguous(), table, target, state)
+        return _FullSortCEMean.apply(output.contiguous(), table, target, state, None)
     return _FullSortCEDir.apply(output.contiguous(), table, target, state).mean()
 
 

@@ -204,6 +204,28 @@ int acattn_full_sort_ce_bwd(const acattn_ce_problem* p, const float* lse, const 
   return rc;
 }
 
+static int check_ce_pair(const acattn_ce_problem* pa, const acattn_ce_problem* pc) {
+  if (int rc = check_ce(pa)) return rc;
+  if (int rc = check_ce(pc)) return rc;
+  if (pa->N != pc->N || pa->H != pc->H) return fail("the two row sets must share the table: N and H differ");
+  return 0;
+}
+
+int64_t acattn_full_sort_ce_fwd_pair_workspace_bytes(const acattn_ce_problem* pa, const acattn_ce_problem* pc) {
+  if (check_ce_pair(pa, pc)) return -1;
+  return acattn_ce_pair_ws_bytes(*pa, *pc);
+}
+
+int acattn_full_sort_ce_fwd_pair(const acattn_ce_problem* pa, const acattn_ce_problem* pc, void* workspace, float* lse_a,
+                                 float* row_loss_a, float* dir_a, float* lse_c, float* row_loss_c, void* stream) {
+  if (int rc = check_ce_pair(pa, pc)) return rc;
+  if (!workspace || !lse_a || !row_loss_a || !dir_a || !lse_c || !row_loss_c)
+    return fail("workspace, lse_a, row_loss_a, dir_a, lse_c, row_loss_c must be non-NULL");
+  const int rc = acattn_launch_ce_fwd_pair(*pa, *pc, workspace, lse_a, row_loss_a, dir_a, lse_c, row_loss_c, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
 int acattn_full_sort_ce_products(int mode) { return acattn_ce_products_choice(mode); }
 
 int acattn_linear_products(int mode) { return acattn_linear_products_choice(mode); }
@@ -503,6 +525,21 @@ int acattn_attacked_loss_finish_rows(const float* row_loss, int32_t B, const flo
   if (n_scale < 0 || (n_scale > 0 && !scale_buf)) return fail("scale_buf must be given with n_scale > 0");
   const int rc = acattn_launch_attacked_loss_finish_rows(row_loss, B, pen, n_masks, count, weight, out, scale_buf, n_scale,
                                                          (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
+int acattn_attacked_loss_finish_rows_pair(const float* row_loss, int32_t B, const float* const* pen, int32_t n_masks,
+                                          int32_t count, float weight, float* out, float* scale_buf, int32_t n_scale,
+                                          const float* row_loss_c, int32_t B_c, float* mean_c, void* stream) {
+  if (!row_loss || !pen || !out) return fail("row_loss, pen and out must be non-NULL");
+  if (!row_loss_c || !mean_c || B_c < 1) return fail("row_loss_c and mean_c must be non-NULL, B_c positive");
+  if (B < 1 || count < 1 || n_masks < 1 || n_masks > ACATTN_MAX_MASKS) return fail("B, count positive, 1 <= n_masks <= ACATTN_MAX_MASKS");
+  for (int l = 0; l < n_masks; ++l)
+    if (!pen[l]) return fail("every pen vector must be non-NULL");
+  if (n_scale < 0 || (n_scale > 0 && !scale_buf)) return fail("scale_buf must be given with n_scale > 0");
+  const int rc = acattn_launch_attacked_loss_finish_rows(row_loss, B, pen, n_masks, count, weight, out, scale_buf, n_scale,
+                                                         (hipStream_t)stream, row_loss_c, B_c, mean_c);
   if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
   return rc;
 }

@@ -189,13 +189,12 @@ __global__ void __launch_bounds__(64 * CE_NW) ce_fwd_kernel(const acattn_ce_prob
   }
 }
 
-// one wave per batch row: fold the partials, add the target logit
+// one wave per batch row: fold the partials, add the target logit (workgroup `blk` of four rows)
 template <int CH>
-__global__ void __launch_bounds__(256) ce_fwd_reduce_kernel(const acattn_ce_problem P, const float2* __restrict__ part,
-                                                            int n_part, float* __restrict__ lse,
-                                                            float* __restrict__ row_loss) {
+__device__ __forceinline__ void fwd_reduce_rows(const acattn_ce_problem& P, const float2* __restrict__ part, int n_part,
+                                                float* __restrict__ lse, float* __restrict__ row_loss, const int blk) {
   const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int row = blk * 4 + (threadIdx.x >> 6);
   if (row >= P.B) return;
   float m = ACATTN_NEG_INF, s = 0.f;
   for (int k = lane; k < n_part; k += 64) {
@@ -231,6 +230,13 @@ __global__ void __launch_bounds__(256) ce_fwd_reduce_kernel(const acattn_ce_prob
     lse[row] = l;
     row_loss[row] = tgt_ok ? l - dot : __builtin_nanf("");
   }
+}
+
+template <int CH>
+__global__ void __launch_bounds__(256) ce_fwd_reduce_kernel(const acattn_ce_problem P, const float2* __restrict__ part,
+                                                            int n_part, float* __restrict__ lse,
+                                                            float* __restrict__ row_loss) {
+  fwd_reduce_rows<CH>(P, part, n_part, lse, row_loss, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -726,13 +732,12 @@ __global__ void __launch_bounds__(256) ce_bwd_reduce_kernel(const float* __restr
 //   m = max_wg m_wg,  w_wg = exp(m_wg - m),  S = sum w_wg s_wg,  O = sum w_wg slab_wg[row]
 //   lse = m + log S,  row_loss = lse - out_row . E_target,  dir = O / S - E_target   (= d row_loss / d out_row)
 template <int CH>
-__global__ void __launch_bounds__(256) ce_dir_reduce_kernel(const acattn_ce_problem P, const float2* __restrict__ part,
-                                                             const float* __restrict__ slab, const int n_wg,
-                                                             float* __restrict__ lse, float* __restrict__ row_loss,
-                                                             float* __restrict__ dir) {
+__device__ __forceinline__ void dir_reduce_row(const acattn_ce_problem& P, const float2* __restrict__ part,
+                                               const float* __restrict__ slab, const int n_wg, float* __restrict__ lse,
+                                               float* __restrict__ row_loss, float* __restrict__ dir, const int row) {
   extern __shared__ float wts[];  // [n_wg] weights, then scratch
   __shared__ float red[256];
-  const int row = blockIdx.x, B = P.B;
+  const int B = P.B;
   float m = ACATTN_NEG_INF;
   for (int k = threadIdx.x; k < n_wg; k += 256) m = fmaxf(m, part[(size_t)k * B + row].x);
   red[threadIdx.x] = m;
@@ -785,6 +790,27 @@ __global__ void __launch_bounds__(256) ce_dir_reduce_kernel(const acattn_ce_prob
     lse[row] = l;
     row_loss[row] = (tgt_raw >= 0 && tgt_raw < P.N) ? l - dot : __builtin_nanf("");
   }
+}
+
+template <int CH>
+__global__ void __launch_bounds__(256) ce_dir_reduce_kernel(const acattn_ce_problem P, const float2* __restrict__ part,
+                                                             const float* __restrict__ slab, const int n_wg,
+                                                             float* __restrict__ lse, float* __restrict__ row_loss,
+                                                             float* __restrict__ dir) {
+  dir_reduce_row<CH>(P, part, slab, n_wg, lse, row_loss, dir, blockIdx.x);
+}
+
+// The paired forward's finish in one launch: workgroup b < Pa.B is ce_dir_reduce_kernel's for row b of set a, the others
+// are ce_fwd_reduce_kernel's for four rows of set c each.
+template <int CH>
+__global__ void __launch_bounds__(256) ce_pair_reduce_kernel(const acattn_ce_problem Pa, const float2* __restrict__ part_a,
+                                                              const float* __restrict__ slab, const int n_part,
+                                                              float* __restrict__ lse_a, float* __restrict__ row_loss_a,
+                                                              float* __restrict__ dir_a, const acattn_ce_problem Pc,
+                                                              const float2* __restrict__ part_c, float* __restrict__ lse_c,
+                                                              float* __restrict__ row_loss_c) {
+  if ((int)blockIdx.x < Pa.B) dir_reduce_row<CH>(Pa, part_a, slab, n_part, lse_a, row_loss_a, dir_a, blockIdx.x);  // (uniform)
+  else fwd_reduce_rows<CH>(Pc, part_c, n_part, lse_c, row_loss_c, blockIdx.x - Pa.B);
 }
 
 constexpr int64_t kSlabLimit = 512ll << 20;  // bytes of d_out slabs above which the backward uses atomics (96 MB until round 3: configs[3] is 136-162 MB and was paying 34 M float atomics per launch)
@@ -1118,7 +1144,40 @@ int launch_bwd(const acattn_ce_problem& p, const float* lse, const float* coef, 
   }
 }
 
+// [round 9] Both losses' forward in one sweep (hidden 64, the split sweeps): workspace = set a's as for launch_fwd_dir
+// (slabs, partials, row images), then set c's row images and partials.  -100 where launch_fwd_dir would not take the
+// split direction sweep.
+bool pair_plan(const acattn_ce_problem& pa, const acattn_ce_problem& pc, int& n_wg, int& n_left) {
+  if (pa.H != 64 || pc.H != 64 || pa.table != pc.table || pa.N != pc.N) return false;
+  if (!ce6_plan<64>(pa.N, n_wg, n_left)) return false;
+  return (n_wg + n_left) * (int64_t)pa.B * 64 * (int64_t)sizeof(float) <= kSlabLimit;
+}
+
 }  // namespace
+
+int64_t acattn_ce_pair_ws_bytes(const acattn_ce_problem& pa, const acattn_ce_problem& pc) {
+  int n_wg, n_left;
+  if (!pair_plan(pa, pc, n_wg, n_left)) return -100;
+  return align256(align256(ws_bytes<64>(pa)) + acattn_ce6_rows_bytes(pc)) + (int64_t)(n_wg + n_left) * pc.B * (int64_t)sizeof(float2);
+}
+
+int acattn_launch_ce_fwd_pair(const acattn_ce_problem& pa, const acattn_ce_problem& pc, void* ws, float* lse_a, float* row_loss_a,
+                              float* dir_a, float* lse_c, float* row_loss_c, hipStream_t stream) {
+  int n_wg, n_left;
+  if (!pair_plan(pa, pc, n_wg, n_left)) return -100;
+  constexpr int CH = 64;
+  const int n_slabs = n_wg + n_left;
+  float* slab = (float*)ws;
+  float2* part_a = (float2*)(slab + (size_t)n_slabs * pa.B * CH);
+  void* rows_a = (char*)ws + align256(ws_bytes_base<CH>(pa));
+  char* rows_c = (char*)ws + align256(ws_bytes<CH>(pa));
+  float2* part_c = (float2*)((char*)ws + align256(align256(ws_bytes<CH>(pa)) + acattn_ce6_rows_bytes(pc)));
+  if (const int e = acattn_launch_ce6_pair_sweep(pa, pc, slab, part_a, rows_a, part_c, rows_c, n_wg, n_left, stream)) return e;
+  const size_t rlds = (size_t)(n_slabs + (256 / (CH / 4)) * CH) * sizeof(float);
+  hipLaunchKernelGGL((ce_pair_reduce_kernel<CH>), dim3(pa.B + (pc.B + 3) / 4), dim3(256), rlds, stream, pa, (const float2*)part_a,
+                     (const float*)slab, n_slabs, lse_a, row_loss_a, dir_a, pc, (const float2*)part_c, lse_c, row_loss_c);
+  return (int)hipGetLastError();
+}
 
 int acattn_ce_products_choice(int mode) {
   const int old = ce_products();

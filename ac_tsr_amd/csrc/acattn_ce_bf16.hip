@@ -68,12 +68,10 @@ __device__ __forceinline__ void dma16(const void* gsrc, void* lds_dst) {
 // One workgroup per super-block of 32 batch rows: the rows' operand images.
 //   slot (2h + s) * 3 + q,  lane (c, g): plane q of out[32 sb + 16 h + c][32 s + 8 g + j]          (P1's B operand)
 //   slot 12 + 4 q + cb,     lane (c, g): plane q of out[32 sb + 8 g + j][16 cb + c]                  (P3's B operand)
-// Also zeroes `n_zero` floats at `zero` (the leftover tiles' d_table rows when several workgroups add into them).
-__global__ void __launch_bounds__(256) ce_split_rows_kernel(const float* __restrict__ out, const int B, b8* __restrict__ Hb,
-                                                            float* __restrict__ zero, const int64_t n_zero) {
-  const int sb = blockIdx.x;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_zero; i += (int64_t)gridDim.x * 256) zero[i] = 0.f;
-  for (int e = threadIdx.x; e < 8 * 64; e += 256) {
+// BY_COL = false leaves the twelve by-column slots unwritten (a row set that only P1 reads).
+template <bool BY_COL>
+__device__ __forceinline__ void split_rows_block(const float* __restrict__ out, const int B, b8* __restrict__ Hb, const int sb) {
+  for (int e = threadIdx.x; e < (BY_COL ? 8 : 4) * 64; e += 256) {
     const int grp = e >> 6, lane = e & 63, c = lane & 15, g = lane >> 4;
     float x[8];
     if (grp < 4) {
@@ -103,6 +101,22 @@ __global__ void __launch_bounds__(256) ce_split_rows_kernel(const float* __restr
       Hb[((size_t)sb * HSLOTS + slot) * 64 + lane] = p[q];
     }
   }
+}
+
+// Also zeroes `n_zero` floats at `zero` (the leftover tiles' d_table rows when several workgroups add into them).
+__global__ void __launch_bounds__(256) ce_split_rows_kernel(const float* __restrict__ out, const int B, b8* __restrict__ Hb,
+                                                            float* __restrict__ zero, const int64_t n_zero) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_zero; i += (int64_t)gridDim.x * 256) zero[i] = 0.f;
+  split_rows_block<true>(out, B, Hb, blockIdx.x);
+}
+
+// The paired forward's two row sets in one launch: the first nsb_a workgroups set a (all 24 slots, as the separate
+// call writes them: the sweep's DMA copies whole images), the rest set c (P1's twelve slots).
+__global__ void __launch_bounds__(256) ce_split_rows_pair_kernel(const float* __restrict__ out_a, const int B_a, b8* __restrict__ Hb_a,
+                                                                 const int nsb_a, const float* __restrict__ out_c, const int B_c,
+                                                                 b8* __restrict__ Hb_c) {
+  if ((int)blockIdx.x < nsb_a) split_rows_block<true>(out_a, B_a, Hb_a, blockIdx.x);
+  else split_rows_block<false>(out_c, B_c, Hb_c, blockIdx.x - nsb_a);
 }
 
 // Diagnostic builds only (-DACATTN_CE_STAMPS, tools/gpu_ce6_stamps.sh): cycles per phase, summed per wave.
@@ -145,13 +159,22 @@ struct Ce6 {
   static_assert(LDS_BYTES <= 160 * 1024, "one workgroup per CU");
 };
 
+// The paired forward's second row set (DIR only; B = 0: none).  It needs lse alone, i.e. P1 and a running (max, sum-exp),
+// and the wave holds P1's table operands already: behind the sweep of the first set the same wave sweeps these rows
+// with Er, one (max, sum-exp) pair per (workgroup or leftover tile, row) into `part`, as ce6_fwd_kernel leaves them.
+struct Ce6Second {
+  const b8* Hb;  // the rows' operand images, ce_split_rows_pair_kernel's (the twelve by-row slots of each super-block)
+  float2* part;  // [n_wg + n_left][B]
+  int B;
+};
+
 // DIR as in acattn_ce.hip: a forward that also yields the direction of d_out (running maxima per wave, folded per
 // workgroup, finished by ce_dir_reduce_kernel).
 template <int TILES, bool WITH_TABLE_GRAD, bool DIR>
 __global__ void __launch_bounds__(64 * NW) ce6_bwd_kernel(const acattn_ce_problem P, const float* __restrict__ lse,
                                                           const float* __restrict__ coef, float* __restrict__ d_out_slab,
                                                           float* __restrict__ d_table, float2* __restrict__ part,
-                                                          const b8* __restrict__ Hb, const int n_left) {
+                                                          const b8* __restrict__ Hb, const int n_left, const Ce6Second S2) {
   static_assert(!(DIR && WITH_TABLE_GRAD), "the forward-with-direction sweep has no table gradient");
   using C = Ce6<TILES>;
   const int lane = threadIdx.x & 63;
@@ -456,6 +479,102 @@ __global__ void __launch_bounds__(64 * NW) ce6_bwd_kernel(const acattn_ce_proble
     __syncthreads();  // the parked tiles are free
     CE6_STAMP(5);
   }
+  if constexpr (DIR) {
+    if (S2.B > 0) {  // (uniform per launch)
+      // ---- the second row set: P1 from the resident Er, max / exp2 / sum; no split of dl, no P2, no parked tile, no slab.
+      // P1, the ragged fix and the soft-max sums are written out again here instead of sharing the first loop's lambdas:
+      // hoisted above both loops (images as a parameter) the same source compiles the OTHER two instantiations differently
+      // (436 instead of 444 registers, another instruction order in the table-gradient sweep), and those were to stay the
+      // measured code.  Keep the two copies in step.
+      // Images by the same LDS-DMA double buffer (both halves are free behind the barrier above), the twelve by-row slots
+      // only, three 1-KB pieces per wave.  The four waves' pairs of a super-block meet in the pad columns of the parked-tile
+      // rows (ES = CH + 4: two pairs, taken by super-block parity) and are folded by the first 32 threads at the top of the
+      // NEXT iteration, as in ce6_fwd_kernel: one barrier per super-block.
+      const int Bc = S2.B, nsbc = (Bc + 31) >> 5;
+      auto dma_rows_c = [&](int sb) {
+        const char* src = (const char*)S2.Hb + (size_t)sb * HB_BYTES + (3 * wave) * 1024 + lane * 16;
+        char* dst = smem + (sb & 1) * HB_BYTES + (3 * wave) * 1024;
+#pragma unroll
+        for (int u = 0; u < 3; ++u) dma16(src + u * 1024, dst + u * 1024);
+      };
+      auto fold_c = [&](int sb) {
+        if (threadIdx.x < 32) {
+          const float* f = park + threadIdx.x * ES + CH + 2 * (sb & 1);
+          float mw[NW], m_wg = ACATTN_NEG_INF;
+#pragma unroll
+          for (int w = 0; w < NW; ++w) {
+            mw[w] = f[w * C::PARK_FLOATS];
+            m_wg = fmaxf(m_wg, mw[w]);
+          }
+          float s_wg = 0.f;
+#pragma unroll
+          for (int w = 0; w < NW; ++w)
+            s_wg += mw[w] > ACATTN_NEG_INF ? f[w * C::PARK_FLOATS + 1] * __builtin_amdgcn_exp2f((mw[w] - m_wg) * kLog2e) : 0.f;
+          const int row = 32 * sb + threadIdx.x;
+          if (row < Bc) S2.part[(size_t)blockIdx.x * Bc + row] = float2{m_wg, s_wg};
+        }
+      };
+      // (Requested here, behind the first loop: one exposed round trip to L2 per workgroup.  Issued inside the first loop's
+      // last iteration instead, the second set's arguments are live across that loop and the sweep spills seven scalar
+      // registers -- it was to stay free of spills.)
+      dma_rows_c(0);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      for (int sb = 0; sb < nsbc; ++sb) {
+        const b8* Hs = (const b8*)(smem + (sb & 1) * HB_BYTES);
+        if (sb + 1 < nsbc) dma_rows_c(sb + 1);  // its buffer was last read before the previous super-block's barrier
+        if (sb > 0) fold_c(sb - 1);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          b8 Hr[2][3];
+#pragma unroll
+          for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) Hr[s][q] = Hs[((2 * h + s) * 3 + q) * 64 + lane];
+          f4 dl[TILES];
+#pragma unroll
+          for (int t = 0; t < TILES; ++t) dl[t] = f4{0.f, 0.f, 0.f, 0.f};
+#define CE6_C1(p, q)                                                                  \
+  _Pragma("unroll") for (int s = 0; s < 2; ++s)                                      \
+      _Pragma("unroll") for (int t = 0; t < TILES; ++t) dl[t] = mfma_bf(Er[t][s][p], Hr[s][q], dl[t]);
+          CE6_TERMS(CE6_C1)
+#undef CE6_C1
+          if (ragged) {
+            // (the bound passes through an empty asm so that the 24 compares are made here: as loop invariants their
+            // masks are 48 scalar registers held across the loop, at the price of spills elsewhere)
+            int n_ok = N - item0 - 4 * g;
+            asm volatile("" : "+v"(n_ok));
+#pragma unroll
+            for (int t = 0; t < TILES; ++t)
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                if (16 * t + r >= n_ok) dl[t][r] = ACATTN_NEG_INF;  // exp2(-inf) = 0 past the catalogue end
+          }
+          float m_w = ACATTN_NEG_INF;
+#pragma unroll
+          for (int t = 0; t < TILES; ++t) m_w = fmaxf(fmaxf(fmaxf(fmaxf(m_w, dl[t][0]), dl[t][1]), dl[t][2]), dl[t][3]);
+          m_w = quad_max(m_w);
+          const float m2 = m_w > ACATTN_NEG_INF ? m_w * kLog2e : 0.f;
+          f4 sv = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int t = 0; t < TILES; ++t) {
+            f4 x = dl[t] * kLog2e - m2;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) x[r] = __builtin_amdgcn_exp2f(x[r]);
+            sv += x;
+          }
+          const float s_w = quad_sum((sv[0] + sv[1]) + (sv[2] + sv[3]));
+          if (g == 0) {
+            Pw[(16 * h + c) * ES + CH + 2 * (sb & 1)] = m_w;
+            Pw[(16 * h + c) * ES + CH + 2 * (sb & 1) + 1] = s_w;
+          }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's share of the next super-block's images has landed
+        __syncthreads();
+      }
+      fold_c(nsbc - 1);
+    }
+  }
   // The wave's d_table rows.  A lane holds, per tile, 16 single floats of four different rows (item 4g + r, channel
   // 16cb + c): stored as they stand that is 96 dword stores of four 64-byte pieces each -- 12,500 cycles per wave,
   // 6 us of the launch (tools/gpu_ce6_stamps.sh, CE6_STAMP_LEFT=1).  Through the wave's parked-tile area instead: a tile
@@ -680,6 +799,64 @@ __global__ void __launch_bounds__(64 * NW) ce6_bwd_kernel(const acattn_ce_proble
         if (itx + i < N) {
           if (pieces > 1) atomicAdd(d_table + (size_t)(itx + i) * CH + hcol, v);
           else d_table[(size_t)(itx + i) * CH + hcol] = v;
+        }
+      }
+    }
+    if constexpr (DIR) {
+      if (S2.B > 0) {
+        // the second row set's units (leftover tile, super-block), dealt out evenly as above: P1 and the soft-max sums on
+        // one item tile, ce6_fwd_kernel's leftover loop
+        const int Bc = S2.B, nsbc = (Bc + 31) >> 5;
+        const int n_units = n_left * nsbc, U = (n_units + gridDim.x * NW - 1) / (gridDim.x * NW);
+        const int first_c = wid * U, n_my_c = min(max(n_units - first_c, 0), U);
+        int cur = -1;
+        b8 Erc[2][3];
+        for (int k = 0; k < n_my_c; ++k) {
+          const int u = first_c + k, tile = u / nsbc, sb = u - tile * nsbc;
+          const int itx = gridDim.x * NW * C::ITEMS + 16 * tile;
+          b8 Hq[12];
+          const b8* src = S2.Hb + (size_t)sb * HSLOTS * 64 + lane;
+#pragma unroll
+          for (int i = 0; i < 12; ++i) Hq[i] = src[i * 64];
+          if (tile != cur) {  // (uniform per wave)
+            cur = tile;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+              const float* tsrc = P.table + (size_t)min(itx + c, N - 1) * CH + 32 * s + 8 * g;
+              const f4 v0 = *(const f4*)tsrc, v1 = *(const f4*)(tsrc + 4);
+              float x[8];
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                x[j] = itx + c < N ? v0[j] : 0.f;
+                x[4 + j] = itx + c < N ? v1[j] : 0.f;
+              }
+              split8(x, Erc[s][0], Erc[s][1], Erc[s][2]);
+            }
+          }
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            f4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
+#define CE6_CL(p, q)                                          \
+  a0 = mfma_bf(Erc[0][p], Hq[(2 * h + 0) * 3 + q], a0);      \
+  a1 = mfma_bf(Erc[1][p], Hq[(2 * h + 1) * 3 + q], a1);
+            CE6_TERMS(CE6_CL)
+#undef CE6_CL
+            f4 a = a0 + a1;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (itx + 4 * g + r >= N) a[r] = ACATTN_NEG_INF;
+            const float m = quad_max(fmaxf(fmaxf(a[0], a[1]), fmaxf(a[2], a[3])));
+            float sum = 0.f;
+            if (m > ACATTN_NEG_INF) {
+              f4 x = a * kLog2e - m * kLog2e;
+#pragma unroll
+              for (int r = 0; r < 4; ++r) x[r] = __builtin_amdgcn_exp2f(x[r]);
+              sum = (x[0] + x[1]) + (x[2] + x[3]);
+            }
+            sum = quad_sum(sum);
+            const int row = 32 * sb + 16 * h + c;
+            if (g == 0 && row < Bc) S2.part[(size_t)(gridDim.x + tile) * Bc + row] = float2{m, sum};
+          }
         }
       }
     }
@@ -944,6 +1121,7 @@ int acattn_launch_ce6_sweep(const acattn_ce_problem& p, const float* lse, const 
                             float2* part, void* rows_ws, int n_wg, int n_left, bool dir, hipStream_t stream) {
   using C = Ce6<6>;
   b8* Hb = (b8*)rows_ws;
+  const Ce6Second none{nullptr, nullptr, 0};
   float* zero = nullptr;
   int64_t n_zero = 0;
   if (d_table && !dir && n_left > 0 && n_wg / n_left > 1) {  // (the kernel's `pieces` > 1)
@@ -956,16 +1134,34 @@ int acattn_launch_ce6_sweep(const acattn_ce_problem& p, const float* lse, const 
   if (dir) {
     auto k = ce6_bwd_kernel<6, false, true>;
     allow_lds(k, lds);
-    hipLaunchKernelGGL(k, dim3(n_wg), dim3(64 * NW), lds, stream, p, lse, coef, slab, d_table, part, (const b8*)Hb, n_left);
+    hipLaunchKernelGGL(k, dim3(n_wg), dim3(64 * NW), lds, stream, p, lse, coef, slab, d_table, part, (const b8*)Hb, n_left, none);
   } else if (d_table) {
     auto k = ce6_bwd_kernel<6, true, false>;
     allow_lds(k, lds);
-    hipLaunchKernelGGL(k, dim3(n_wg), dim3(64 * NW), lds, stream, p, lse, coef, slab, d_table, part, (const b8*)Hb, n_left);
+    hipLaunchKernelGGL(k, dim3(n_wg), dim3(64 * NW), lds, stream, p, lse, coef, slab, d_table, part, (const b8*)Hb, n_left, none);
   } else {
     auto k = ce6_bwd_kernel<6, false, false>;
     allow_lds(k, lds);
-    hipLaunchKernelGGL(k, dim3(n_wg), dim3(64 * NW), lds, stream, p, lse, coef, slab, d_table, part, (const b8*)Hb, n_left);
+    hipLaunchKernelGGL(k, dim3(n_wg), dim3(64 * NW), lds, stream, p, lse, coef, slab, d_table, part, (const b8*)Hb, n_left, none);
   }
+  return (int)hipGetLastError();
+}
+
+// The paired forward: one row-split launch for both sets, then the direction sweep of set a with set c's lse sweep behind
+// it in the same waves.  Set a's slabs / partials as acattn_launch_ce6_sweep(dir = true) leaves them; set c's partials
+// ((n_wg + n_left) x pc.B pairs) in part_c.
+int acattn_launch_ce6_pair_sweep(const acattn_ce_problem& pa, const acattn_ce_problem& pc, float* slab, float2* part_a,
+                                 void* rows_a, float2* part_c, void* rows_c, int n_wg, int n_left, hipStream_t stream) {
+  using C = Ce6<6>;
+  const int nsb_a = (pa.B + 31) / 32, nsb_c = (pc.B + 31) / 32;
+  hipLaunchKernelGGL(ce_split_rows_pair_kernel, dim3(nsb_a + nsb_c), dim3(256), 0, stream, pa.out, pa.B, (b8*)rows_a, nsb_a,
+                     pc.out, pc.B, (b8*)rows_c);
+  const size_t lds = C::LDS_BYTES;
+  const Ce6Second second{(const b8*)rows_c, part_c, pc.B};
+  auto k = ce6_bwd_kernel<6, false, true>;
+  allow_lds(k, lds);
+  hipLaunchKernelGGL(k, dim3(n_wg), dim3(64 * NW), lds, stream, pa, (const float*)nullptr, (const float*)nullptr, slab,
+                     (float*)nullptr, part_a, (const b8*)rows_a, n_left, second);
   return (int)hipGetLastError();
 }
 

@@ -378,7 +378,8 @@ void acattn_penalty_written_set(bool v);
 bool acattn_penalty_written();
 int acattn_launch_penalty_rows(const float* m, int B, int nh, int L, float* pen, hipStream_t stream);
 int acattn_launch_attacked_loss_finish_rows(const float* row_loss, int B, const float* const* pen, int n_masks, int count,
-                                            float weight, float* out, float* scale_buf, int n_scale, hipStream_t stream);
+                                            float weight, float* out, float* scale_buf, int n_scale, hipStream_t stream,
+                                            const float* row_loss_c = nullptr, int B_c = 0, float* mean_c = nullptr);
 int acattn_launch_penalty_drows(const float* norms, const float* d_loss, float scale, int count, float* const* d_pen,
                                 int n_masks, hipStream_t stream, const float* dir = nullptr, float* d_out = nullptr, int n_dir = 0);
 int acattn_launch_attacked_loss_finish(const float* row_loss, int B, const float* part, int n_masks, int64_t mask_numel,
@@ -396,6 +397,12 @@ int acattn_launch_ce6_sweep(const acattn_ce_problem& p, const float* lse, const 
 int acattn_launch_ce6_onehot_reduce(const acattn_ce_problem& p, const float* coef, const float* slab, int n_slabs, float* d_out,
                                     float* d_table, hipStream_t stream);
 int acattn_launch_ce6_fwd_sweep(const acattn_ce_problem& p, float2* part, void* rows_ws, int n_wg, int n_left, hipStream_t stream);
+int acattn_launch_ce6_pair_sweep(const acattn_ce_problem& pa, const acattn_ce_problem& pc, float* slab, float2* part_a,
+                                 void* rows_a, float2* part_c, void* rows_c, int n_wg, int n_left, hipStream_t stream);
+// acattn_ce.hip: both losses' forward in one sweep (-100: the paired form does not apply)
+int64_t acattn_ce_pair_ws_bytes(const acattn_ce_problem& pa, const acattn_ce_problem& pc);
+int acattn_launch_ce_fwd_pair(const acattn_ce_problem& pa, const acattn_ce_problem& pc, void* ws, float* lse_a, float* row_loss_a,
+                              float* dir_a, float* lse_c, float* row_loss_c, hipStream_t stream);
 int acattn_ce_products_choice(int mode);
 int acattn_linear_products_choice(int mode);
 int acattn_launch_dense_ce_fwd(const float* logits, int64_t rows, int64_t N, const int64_t* target, float* lse, float* row_loss,

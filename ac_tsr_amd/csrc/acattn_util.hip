@@ -247,11 +247,15 @@ struct PenaltyRows {
   float* d_pen[ACATTN_MAX_MASKS];
 };
 
-// attacked_loss_finish_kernel with one pen vector per mask (see there)
+// attacked_loss_finish_kernel with one pen vector per mask (see there).  row_loss_c (or NULL): a second set of B_c row
+// losses whose mean goes to mean_c[0] -- the calibrated loss of the paired cross-entropy forward, summed in this launch's
+// fixed order instead of by a launch of its own.
 __global__ void __launch_bounds__(256) attacked_loss_finish_rows_kernel(const float* __restrict__ row_loss, const int B,
                                                                         const PenaltyRows R, const int n_masks, const int count,
                                                                         const float weight, float* __restrict__ out,
-                                                                        float* __restrict__ scale_buf, const int n_scale) {
+                                                                        float* __restrict__ scale_buf, const int n_scale,
+                                                                        const float* __restrict__ row_loss_c, const int B_c,
+                                                                        float* __restrict__ mean_c) {
   const float k = -1.0f / (float)B;
   if (blockIdx.x > 0) {
     for (int i = (blockIdx.x - 1) * 256 + threadIdx.x; i < n_scale / 4; i += (gridDim.x - 1) * 256)
@@ -304,6 +308,10 @@ __global__ void __launch_bounds__(256) attacked_loss_finish_rows_kernel(const fl
     out[0] = weight * (pen / (float)n_masks) - ce;
     out[1] = ce;
   }
+  if (row_loss_c) {  // (uniform)
+    const float mc = block_sum(thread_sum(row_loss_c, B_c)) / (float)B_c;
+    if (threadIdx.x == 0) mean_c[0] = mc;
+  }
 }
 
 // d_pen[l][:] = d_loss * scale / (2 norm_l); slice blockIdx.y == n_masks (when launched): d_out[:] = dir[:] * d_loss, the
@@ -332,12 +340,13 @@ int acattn_launch_penalty_rows(const float* m, int B, int nh, int L, float* pen,
 }
 
 int acattn_launch_attacked_loss_finish_rows(const float* row_loss, int B, const float* const* pen, int n_masks, int count,
-                                            float weight, float* out, float* scale_buf, int n_scale, hipStream_t stream) {
+                                            float weight, float* out, float* scale_buf, int n_scale, hipStream_t stream,
+                                            const float* row_loss_c, int B_c, float* mean_c) {
   PenaltyRows R{};
   for (int l = 0; l < n_masks; ++l) R.pen[l] = pen[l];
   const int scale_wgs = n_scale > 0 ? std::min((n_scale / 4 + 255) / 256 + 1, 64) : 0;
   hipLaunchKernelGGL(attacked_loss_finish_rows_kernel, dim3(1 + scale_wgs), dim3(256), 0, stream, row_loss, B, R, n_masks,
-                     count, weight, out, scale_buf, n_scale);
+                     count, weight, out, scale_buf, n_scale, row_loss_c, B_c, mean_c);
   return (int)hipGetLastError();
 }
 

@@ -227,7 +227,12 @@ class ACSASRec(SequentialRecommender):
         if attacked_output is not None:
             if (self.loss_type == 'CE' and not self.trainable_mask_loss_weight and attacked_output.is_cuda
                     and ce.supported(self.hidden_size) and torch.is_grad_enabled() and self.dp_mask_penalty == 'local'):
-                # the whole expression below as one node (CE sweep with its direction, one finishing launch)
+                # both losses from ONE forward sweep of the catalogue where that applies (ce.paired_losses) ...
+                both = ce.paired_losses(attacked_output, calibrated_output, self.item_embedding.weight,
+                                        interaction[self.POS_ITEM_ID], all_attack_masks, self.mask_loss_weight, self.step_state)
+                if both is not None:
+                    return both
+                # ... else the whole expression below as one node (CE sweep with its direction, one finishing launch)
                 final_attacked_loss = ce.attacked_loss(attacked_output, self.item_embedding.weight,
                                                        interaction[self.POS_ITEM_ID], all_attack_masks,
                                                        self.mask_loss_weight, self.step_state)

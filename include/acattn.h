@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define ACATTN_ABI_VERSION 33
+#define ACATTN_ABI_VERSION 34
 
 /* attention-mask encodings (recbole/model/abstract_recommender.py:136-143 builds the dense form) */
 enum {
@@ -220,6 +220,18 @@ int acattn_full_sort_ce_fwd(const acattn_ce_problem* p, void* workspace, float* 
 int acattn_full_sort_ce_fwd_dir(const acattn_ce_problem* p, void* workspace, float* lse, float* row_loss, float* dir,
                                 void* stream);
 
+/* [ABI 34] The forward of two row sets over ONE sweep of the table: set a (`pa`) gets what acattn_full_sort_ce_fwd_dir
+ * gives (bit for bit), set c (`pc`) what acattn_full_sort_ce_fwd gives (its partial sums are grouped per workgroup instead
+ * of per wave pair).  The attacked and the calibrated loss of a training step (acsasrec.py:123-138) are such a pair: same
+ * table, same targets, different rows.  pa and pc must share table, N and H; B and target may differ.  Four launches
+ * (row split, sweep, finish; the caller's acattn_attacked_loss_finish_rows_pair) replace eight.
+ * Both return -100 (no error text) when the paired form does not apply -- hidden size other than 64, the exact-fp32
+ * products or a catalogue the split sweeps do not take, set a's slabs beyond their budget, different tables -- and
+ * the caller falls back to the two separate calls.  `workspace`: acattn_full_sort_ce_fwd_pair_workspace_bytes bytes. */
+int64_t acattn_full_sort_ce_fwd_pair_workspace_bytes(const acattn_ce_problem* pa, const acattn_ce_problem* pc);
+int acattn_full_sort_ce_fwd_pair(const acattn_ce_problem* pa, const acattn_ce_problem* pc, void* workspace, float* lse_a,
+                                 float* row_loss_a, float* dir_a, float* lse_c, float* row_loss_c, void* stream);
+
 /* Gradients of sum_b coef[b] * row_loss[b]: d_out [B,H] always; d_table [N,H] (fully overwritten) unless NULL. */
 int acattn_full_sort_ce_bwd(const acattn_ce_problem* p, const float* lse, const float* coef, void* workspace,
                             float* d_out, float* d_table, void* stream);
@@ -360,6 +372,11 @@ int acattn_mask_penalty_bwd_scaled(const float* m, const float* norm, const floa
 int acattn_mask_penalty_rows(const float* m, int32_t B, int32_t n_heads, int32_t L, float* pen, void* stream);
 int acattn_attacked_loss_finish_rows(const float* row_loss, int32_t B, const float* const* pen, int32_t n_masks, int32_t count,
                                      float weight, float* out, float* scale_buf, int32_t n_scale, void* stream);
+/* [ABI 34] acattn_attacked_loss_finish_rows + mean_c[0] = mean(row_loss_c[0 .. B_c)) in the same launch, summed in a fixed
+ * order (the calibrated loss behind acattn_full_sort_ce_fwd_pair, without a reduction launch of its own). */
+int acattn_attacked_loss_finish_rows_pair(const float* row_loss, int32_t B, const float* const* pen, int32_t n_masks,
+                                          int32_t count, float weight, float* out, float* scale_buf, int32_t n_scale,
+                                          const float* row_loss_c, int32_t B_c, float* mean_c, void* stream);
 int acattn_mask_penalty_drows(const float* norms, const float* d_loss, float scale, int32_t count, float* const* d_pen,
                               int32_t n_masks, void* stream);
 /* [ABI 29] acattn_mask_penalty_drows + d_out[:] = direction[:] * d_loss[0] (n_dir floats; the attacked loss's output
