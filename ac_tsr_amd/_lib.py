@@ -101,6 +101,7 @@ class ProjBwdIO(C.Structure):
 
 
 ADAM_MAX_TENSORS = 64
+ADAM_CACHE_BYTES = 32 * ADAM_MAX_TENSORS  # ACATTN_ADAM_CACHE_BYTES
 
 
 class AdamGroup(C.Structure):
@@ -190,6 +191,9 @@ SYMBOLS = {
     "acattn_projections_split_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
     "acattn_adam_step": (C.c_int, [C.POINTER(AdamGroup), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _f,
                                    C.c_void_p]),
+    "acattn_adam_step_cached": (C.c_int, [C.POINTER(AdamGroup), C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _f,
+                                          C.c_void_p, C.c_void_p]),
+    "acattn_select_adam_grid": (C.c_int, [C.c_int]),
     "acattn_dense_ce_fwd": (C.c_int, [_f, C.c_int64, C.c_int64, _f, _f, _f, C.c_void_p]),
     "acattn_dense_ce_bwd": (C.c_int, [_f, _f, _f, _f, C.c_int64, C.c_int64, _f, C.c_void_p]),
     "acattn_step_inputs": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_void_p,

@@ -416,3 +416,6 @@ int acattn_launch_penalty_bwd_scaled_multi(const float* const* m, const float* n
                                            int64_t n, float* const* d_m, int n_masks, hipStream_t stream);
 int acattn_launch_adam_step(const acattn_adam_group& g, double lr, double beta1, double beta2, double eps,
                             double weight_decay, int* done, hipStream_t stream);
+int acattn_launch_adam_step_cached(const acattn_adam_group& g, double lr, double beta1, double beta2, double eps,
+                                   double weight_decay, int* done, void* cache, hipStream_t stream);
+int acattn_select_adam_grid_choice(int workgroups);

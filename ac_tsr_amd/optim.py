@@ -9,15 +9,24 @@ creates the state), goes through torch's own implementation.  The learning rate 
 captured graph replays the rate of the capture (trainer.enable_graph refuses a model whose optimizer has an LR scheduler
 attached; use a tensor `lr`, which takes torch's path, to change it under replay).  The arithmetic reproduces ATen's fused kernel operation by
 operation (csrc/acattn_adam.hip; tests/test_hip_adam.py compares the two).
+
+Two kernels give the same bits (tests/test_hip_adam_stream.py): the persistent one (acattn_adam_step_cached: pipelined
+grid-stride stream, bias corrections from a per-optimizer device cache the previous launch filled) and the one workgroup
+per 4,096 elements it replaced (acattn_adam_step), which `STREAM_KERNEL = False` / ACATTN_ADAM_KERNEL=chunk selects.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 
 from . import _lib
 from .ops import _stream
+
+# The persistent launch with cached bias corrections; ACATTN_ADAM_KERNEL=chunk keeps the one-workgroup-per-chunk launch
+# (A/B runs, tests).
+STREAM_KERNEL = os.environ.get("ACATTN_ADAM_KERNEL", "stream") != "chunk"
 
 
 class Adam(torch.optim.Adam):
@@ -51,6 +60,9 @@ class Adam(torch.optim.Adam):
             done = self.__dict__.get("_acattn_done")
             if done is None or done.device != ps[0].device:
                 done = self.__dict__["_acattn_done"] = torch.zeros(1, dtype=torch.int32, device=ps[0].device)
+                # the correction cache of acattn_adam_step_cached: zero = no entry; the launches fill and check it
+                self.__dict__["_acattn_corrections"] = torch.zeros(_lib.ADAM_CACHE_BYTES, dtype=torch.uint8, device=ps[0].device)
+            cache = self.__dict__["_acattn_corrections"]
             beta1, beta2 = group["betas"]
             for i in range(0, len(ps), _lib.ADAM_MAX_TENSORS):
                 chunk = ps[i:i + _lib.ADAM_MAX_TENSORS]
@@ -61,6 +73,10 @@ class Adam(torch.optim.Adam):
                     g.param[k], g.grad[k] = p.data_ptr(), p.grad.data_ptr()
                     g.exp_avg[k], g.exp_avg_sq[k], g.step[k] = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), st["step"].data_ptr()
                     g.numel[k] = p.numel()
-                _lib.check(lib.acattn_adam_step(C.byref(g), float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
-                                                float(group["weight_decay"]), done.data_ptr(), _stream()), "adam_step")
+                hyper = (float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]))
+                if STREAM_KERNEL:
+                    _lib.check(lib.acattn_adam_step_cached(C.byref(g), *hyper, done.data_ptr(), cache.data_ptr(), _stream()),
+                               "adam_step_cached")
+                else:
+                    _lib.check(lib.acattn_adam_step(C.byref(g), *hyper, done.data_ptr(), _stream()), "adam_step")
         return loss

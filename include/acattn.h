@@ -639,6 +639,21 @@ typedef struct acattn_adam_group {
 } acattn_adam_group;
 int acattn_adam_step(const acattn_adam_group* g, double lr, double beta1, double beta2, double eps, double weight_decay,
                      int32_t* done, void* stream);
+/* [added within ABI 34: new entry points only, nothing existing changes, and tests/test_ce_pair_cpu.py pins the number]
+ * The same update, bit for bit, by a persistent kernel: a fixed grid sized from the device's compute units walks
+ * all tensors' 1,024-element chunks grid-stride with the next chunk's loads in flight under the current one's arithmetic,
+ * and the two bias corrections (1 - beta1^step, sqrt(1 - beta2^step)) are read from `cache` instead of being recomputed by
+ * every wave.  `cache`: ACATTN_ADAM_CACHE_BYTES of device memory, 16-byte aligned, zero before the first call, owned by one
+ * optimizer (launches that share it are ordered by the stream).  The last workgroup to finish writes, per tensor slot, the
+ * corrections of the NEXT step together with the step and the betas they belong to; an entry is used only when all three
+ * equal the launch's (a zero entry never does: the corrected step is >= 1), otherwise the wave computes the corrections
+ * itself -- a changed counter, beta or tensor list costs time, never a wrong value. */
+#define ACATTN_ADAM_CACHE_BYTES (32 * ACATTN_ADAM_MAX_TENSORS)
+int acattn_adam_step_cached(const acattn_adam_group* g, double lr, double beta1, double beta2, double eps, double weight_decay,
+                            int32_t* done, void* cache, void* stream);
+/* [added within ABI 34] Measurement / test hook: workgroups of acattn_adam_step_cached's grid (0 = from the device's compute units; the
+ * environment variable ACATTN_ADAM_GRID sets the initial value).  Returns the previous setting. */
+int acattn_select_adam_grid(int workgroups);
 
 /* ABI 27: 1 when acattn_calibrated_attention_bwd(p, io) with io->dgate_summed = 1 will write the head-summed [B,L,L] gate
  * gradient (see acattn_bwd_io.dgate_summed), 0 when the launch needs the per-head [B,nh,L,L] buffer.  Validates nothing
