@@ -7,6 +7,7 @@ did -- and nothing imports ops or dispatch.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import Optional
@@ -113,13 +114,33 @@ def gate_summed_rule(B: int, L: int, H: int, n_heads: int, n_read_rows: int, blo
     """gate_summed() below without a library or pointers, for shape functions (Meta / fake tensors): the operator form
     under the default environment and ACATTN_BWD_AUTO.  One read position per sequence, no block bitmap, not attack-only:
     the one-row backward, alone or (mask cotangent, L <= 64, dh <= 64) behind the mask-only launch of the split
-    (csrc/acattn_bwd.hip: acattn_bwd_gate_summed; tests/test_hip_onehop.py compares the two)."""
+    (csrc/acattn_bwd.hip: acattn_bwd_gate_summed; tests/test_hip_onehop.py compares the two).  A pinned backward kernel
+    (backward_kernel below) is not known here: a read-row launch under a pin writes [B,nh,L,L] where this rule says
+    [B,1,L,L], so fake-tensor tracing of the backward is only right under ACATTN_BWD_AUTO; the pin is for measurements."""
     dh = H // n_heads
     if n_read_rows != 1 or block_bitmap or attack_only or L > 208 or dh not in (16, 32, 64, 128):
         return False
     if B * n_heads * L * L >= 1 << 30 or B * L * H >= 1 << 30:
         return False
     return not mask_cotangent or (L <= 64 and dh <= 64)
+
+
+def backward_kernel_choice(lib) -> int:
+    """The calling thread's acattn_select_backward_kernel setting (an out-of-range argument changes nothing)."""
+    return lib.acattn_select_backward_kernel(-1)
+
+
+@contextlib.contextmanager
+def backward_kernel(lib, which: int):
+    """acattn_select_backward_kernel is per host thread, and autograd runs the backward of a node with HIP tensors on a
+    worker thread of its own, where a kernel pinned by the thread that built the graph is not in force.  The forward records
+    its thread's setting (backward_kernel_choice) and the backward issues its launches under it, on whichever thread it
+    runs (tests/test_hip_attention_bwd_fp64.py asserts that a pinned kernel is the one that ran)."""
+    prev = lib.acattn_select_backward_kernel(which)
+    try:
+        yield
+    finally:
+        lib.acattn_select_backward_kernel(prev)
 
 
 def gate_summed(lib, prob, io) -> bool:

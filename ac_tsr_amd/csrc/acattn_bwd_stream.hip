@@ -348,7 +348,10 @@ __device__ __forceinline__ void load_row(const acattn_problem& P, const acattn_b
   // a row without any allowed key (left padding) spreads over every key < L; the forward added its -10000 shift to
   // the stored normalisers (acattn_fwd_body.inc), which is taken out again here
   R.dead = P.causal ? F.first_valid > R.i : !F.any_valid;
-  const float sh = R.dead ? ACATTN_MASK_FILL : 0.f;
+  // (a row past L borrows row 0's statistics: the shift taken out is the one ROW 0 carries, or under left padding the
+  // mask fill of such a row would cancel against it and leave probabilities that are not 0)
+  const bool shifted = R.row_ok ? R.dead : (P.causal ? F.first_valid > 0 : !F.any_valid);
+  const float sh = shifted ? ACATTN_MASK_FILL : 0.f;
   const float* sp = IO.row_stats + (bh * L + (R.row_ok ? R.i : 0)) * ACATTN_NSTAT;
   const f4 s0 = *(const f4*)sp;
   const float s4v = sp[4];
@@ -384,7 +387,8 @@ __device__ __forceinline__ void load_mask_row(const acattn_problem& P, const aca
     for (int e = 0; e < 4; ++e) R.qaf[4 * s4 + e] = R.row_ok ? ta[e] : 0.f;
   }
   R.dead = P.causal ? F.first_valid > R.i : !F.any_valid;
-  const float sh = R.dead ? ACATTN_MASK_FILL : 0.f;
+  const bool shifted = R.row_ok ? R.dead : (P.causal ? F.first_valid > 0 : !F.any_valid);  // (see load_row)
+  const float sh = shifted ? ACATTN_MASK_FILL : 0.f;
   R.ly2 = (IO.row_stats[(bh * L + (R.row_ok ? R.i : 0)) * ACATTN_NSTAT + 1] - sh) * kLog2e;
   R.rng_row = (uint32_t)(bh * L + R.i);
 }
@@ -785,8 +789,9 @@ __global__ void __launch_bounds__(64, DH >= ACATTN_BWD_ONE_WAVE_DH ? 1 : 2) acat
   f4 dco = {0.f, 0.f, 0.f, 0.f}, dcd = dco;  // d (key half of the affines) of keys 16 t + 4 g + r, summed over queries at the end
 
   // query blocks that see this key tile: under the causal mask qb >= t; a tile past the last real item is only seen
-  // by blocks with a dead row (they spread over every key)
-  const int qb_lo = causal ? t : 0;
+  // by blocks with a dead row (they spread over every key), and so is ANY tile by the blocks in front of it that hold one
+  // (left padding: first_valid > 0; the test on nt_q below skips the blocks in front that hold none)
+  const int qb_lo = causal && F.first_valid == 0 ? t : 0;
   for (int qb = qb_lo; qb < nT; ++qb) {
     const int i0 = 16 * qb;
     const bool rows_see_a_key = causal ? F.first_valid <= i0 : F.any_valid;

@@ -191,6 +191,7 @@ def _setup_context(ctx, inputs, output):
      gate_is_prob, affine, adversarial) = inputs[:20]
     ctx.adversarial, ctx.has_seed_tensor = adversarial, seed_tensor is not None
     ctx.set_materialize_grads(False)
+    ctx.bwd_kernel = attn_launch.backward_kernel_choice(_lib.load())  # this thread's pin, for the backward's (attn_launch.py)
     seed_t = seed_tensor if seed_tensor is not None else q.new_empty(0)
     if adversarial:
         ctx.args = (causal, n_heads, p_drop, seed, gate_is_prob)
@@ -219,10 +220,11 @@ def _backward(ctx, d_att, d_cal, d_M, _d_stats, d_pen=None):
     q, k, v, qa, ka, gate, key_valid, w_order, b_order, w_dist, b_dist, scalar, seed_t, M, stats = ctx.saved_tensors
     causal, n_heads, p_drop, seed, gate_is_prob = ctx.args
     con = lambda t: None if t is None else t.contiguous()
-    dq, dk, dv, dqa, dka, dgate_part, part = torch.ops.acattn.calibrated_attention_bwd(
-        q, k, v, qa, ka, gate, key_valid, causal, w_order, b_order, w_dist, b_dist, scalar, n_heads, p_drop, seed,
-        seed_t if ctx.has_seed_tensor else None, gate_is_prob, M, stats, con(d_att), con(d_cal), con(d_M), None, None, False,
-        con(d_pen))
+    with attn_launch.backward_kernel(_lib.load(), ctx.bwd_kernel):
+        dq, dk, dv, dqa, dka, dgate_part, part = torch.ops.acattn.calibrated_attention_bwd(
+            q, k, v, qa, ka, gate, key_valid, causal, w_order, b_order, w_dist, b_dist, scalar, n_heads, p_drop, seed,
+            seed_t if ctx.has_seed_tensor else None, gate_is_prob, M, stats, con(d_att), con(d_cal), con(d_M), None, None, False,
+            con(d_pen))
     grads = attn_launch.unpack_partials(part.sum(0), q.shape[-1] // n_heads, w_order, b_order, w_dist, b_dist, scalar)
     dgate = dgate_part[:, 0] if dgate_part.shape[1] == 1 else dgate_part.sum(1)
     return (dq, dk, dv, dqa, dka, dgate, None, None) + grads[:5] + (None,) * 8

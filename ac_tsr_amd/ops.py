@@ -171,6 +171,7 @@ class _CalibratedAttention(torch.autograd.Function):
         B, L, H = q.shape
         ctx.attack_upstream = attack_upstream
         ctx.state = state
+        ctx.bwd_kernel = attn_launch.backward_kernel_choice(lib)  # this thread's pin, for the backward's (attn_launch.py)
         ctx.set_materialize_grads(False)  # an output nobody differentiated arrives as None, not as a zero tensor
         ctx.active_qblocks = None
         ctx.read_rows = None
@@ -238,16 +239,18 @@ class _CalibratedAttention(torch.autograd.Function):
         # pass 2 through a layer with nothing attack-related upstream: only the attack transforms' inputs matter
         attack_only = ctx.state.attack_pass_only and not ctx.attack_upstream
         if ctx.via_dispatcher:
-            res = torch.ops.acattn.calibrated_attention_bwd(
-                q, k, v, qa, ka, gate_logits, ctx.mask.key_valid, bool(ctx.mask.causal), wo.contiguous(), b_order,
-                wd.contiguous(), b_dist, scalar, nh, float(ctx.p_drop), int(ctx.seed) & 0x7FFFFFFFFFFFFFFF, ctx.seed_tensor,
-                bool(ctx.gate_is_prob), M, stats, d_att, d_cal, d_M, ctx.read_rows, ctx.active_qblocks, bool(attack_only), d_pen)
+            with attn_launch.backward_kernel(lib, ctx.bwd_kernel):
+                res = torch.ops.acattn.calibrated_attention_bwd(
+                    q, k, v, qa, ka, gate_logits, ctx.mask.key_valid, bool(ctx.mask.causal), wo.contiguous(), b_order,
+                    wd.contiguous(), b_dist, scalar, nh, float(ctx.p_drop), int(ctx.seed) & 0x7FFFFFFFFFFFFFFF, ctx.seed_tensor,
+                    bool(ctx.gate_is_prob), M, stats, d_att, d_cal, d_M, ctx.read_rows, ctx.active_qblocks, bool(attack_only), d_pen)
         else:
             prob = _fill_problem(q, k, v, qa, ka, gate_logits, ctx.mask, wo, b_order, wd, b_dist, scalar, rich_ratio, cfg,
                                  ctx.p_drop, ctx.rnd, ctx.seed, keep, ctx.seed_tensor, ctx.gate_is_prob)
-            res = attn_launch.attention_bwd_launch(
-                lib, prob, q, nh, M, stats, d_att=d_att, d_cal=d_cal, d_M=d_M, d_pen=d_pen, read_rows=ctx.read_rows,
-                active_qblocks=ctx.active_qblocks, attack_only=attack_only, gate=cfg.combine_option == "gate")
+            with attn_launch.backward_kernel(lib, ctx.bwd_kernel):
+                res = attn_launch.attention_bwd_launch(
+                    lib, prob, q, nh, M, stats, d_att=d_att, d_cal=d_cal, d_M=d_M, d_pen=d_pen, read_rows=ctx.read_rows,
+                    active_qblocks=ctx.active_qblocks, attack_only=attack_only, gate=cfg.combine_option == "gate")
         return _CalibratedAttention._finish_backward(lib, attack_only, *res, dh, w_order, b_order, w_dist, b_dist, scalar,
                                                      rich_ratio, ctx.state)
 
@@ -305,9 +308,10 @@ class _CalibratedAttention(torch.autograd.Function):
                                         w_dist.reshape(-1).contiguous(), b_dist, scalar, nh, float(ctx.p_drop),
                                         int(ctx.seed) & 0x7FFFFFFFFFFFFFFF, ctx.seed_tensor, key_valid=ctx.mask.key_valid,
                                         causal=bool(ctx.mask.causal), gate_is_prob=bool(ctx.gate_is_prob))
-        res = attn_launch.attention_bwd_launch(
-            lib, prob, q, nh, M, stats, d_cal=d_cal1.contiguous(),
-            second=(None if d_cal2 is None else d_cal2.contiguous(), None if d_pen2 is None else d_pen2.contiguous()))
+        with attn_launch.backward_kernel(lib, ctx.bwd_kernel):
+            res = attn_launch.attention_bwd_launch(
+                lib, prob, q, nh, M, stats, d_cal=d_cal1.contiguous(),
+                second=(None if d_cal2 is None else d_cal2.contiguous(), None if d_pen2 is None else d_pen2.contiguous()))
         if res is None:
             return None
         dqa2, dka2 = res[7:]

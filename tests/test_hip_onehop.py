@@ -10,7 +10,12 @@ oracle/ac_tsr_ref.py::core_from_projected (and its autograd) fed the kernels' ow
 the projections launch and in acattn_spatial_affines.
 
 Tolerances: M 5e-6, contexts 1e-4 (north_star: logits within 1e-4); gradients 2e-3 of each tensor's largest magnitude
-(the oracle differentiates the materialised formulation, the kernels the rank-1 / log-normaliser formulation)."""
+against the oracle's autograd in FLOAT32 (the cap of every gradient test: the float32 oracle at these inputs is itself up
+to 7e-3 from a float64 one at head size 128, so nothing tighter can be asked of it).  The tight pin of the backward
+kernels -- the same shapes and cotangent patterns against the oracle in float64, at max(1e-4, 2 * the float32 oracle's own
+error), with better-conditioned calibrator weights -- lives in tests/test_hip_attention_bwd_fp64.py; the 2e-3 comparisons
+that remain here and in tests/test_hip_backward.py are those against float32 references (golden gradients, fully masked
+rows)."""
 import ctypes as C
 import math
 

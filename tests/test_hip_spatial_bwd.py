@@ -18,7 +18,6 @@ quantisation, which a float64 oracle does not reproduce: those rows get a zero c
 checked on their own against the float32 oracle at the 2e-3 cap.  The measured figures are printed per case and gradient
 (profiles/spatial_bwd_accuracy.txt holds a run).
 """
-import contextlib
 import math
 
 import pytest
@@ -27,6 +26,7 @@ import torch
 import ac_tsr_amd as A
 from ac_tsr_amd import attn_launch, dispatch, ops  # noqa: F401  (dispatch: registers torch.ops.acattn.*)
 from oracle import ac_tsr_ref as O
+from tests._attention_fp64 import default_dtype as _default_dtype, err as _err  # shared with test_hip_attention_bwd_fp64.py
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -48,16 +48,6 @@ def _problem(B, L, H, nh, seed, causal=True, scale=0.3, left_pad=False):
     if left_pad:
         kv[1] = 1 - kv[1]
     return t, kv, lens, g
-
-
-@contextlib.contextmanager
-def _default_dtype(dtype):
-    old = torch.get_default_dtype()
-    torch.set_default_dtype(dtype)  # the oracle creates its constants (zeros, the distance table) in the default dtype
-    try:
-        yield
-    finally:
-        torch.set_default_dtype(old)
 
 
 def _leaf_names(terms):
@@ -111,10 +101,6 @@ def _kernel_grads(t, mask_dev, nh, terms, p_drop, G, seed=None, rnd=None, read_r
         second = torch.autograd.grad(loss, leaves)
         return out, {n: g.detach().cpu() for n, g in zip(names, second)}
     return out
-
-
-def _err(got, ref):
-    return ((got.double() - ref.double()).abs().max() / ref.double().abs().max().clamp_min(1e-300)).item()
 
 
 def _setup(B, L, H, nh, mask_kind, causal, left_pad, p_drop, scale, rng):
