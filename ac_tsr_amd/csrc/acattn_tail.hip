@@ -2016,6 +2016,17 @@ __global__ void __launch_bounds__(64 * NWV, H > 128 ? 1 : (H < 128 ? ACATTN_TAIL
   });
 }
 
+// waves that share a row block in the forward below wide_split().  tail_wide_fwd_kernel asks for two W1 slabs ahead, so a
+// wave needs at least two of the I / 16 slabs: inner 64 runs with two waves of two slabs, which measured faster at 512
+// rows than four waves of one slab each with nothing requested ahead (profiles/tail_128_64_ab.txt).
+template <int I>
+constexpr int wide_fwd_waves() { return I >= 128 ? 4 : 2; }
+
+// tail_transpose_kernel's grid: 16 x 16 tiles along the longer side of the widest matrix (Wd is H x H also where I < H;
+// blocks outside a matrix return)
+template <int H, int I>
+constexpr int transpose_tiles() { return (H > I ? H : I) / 16; }
+
 template <int H, int I>
 int launch_wide_fwd(const acattn_tail_problem& p, const acattn_tail_saved& s, hipStream_t stream) {
   const int blocks = (p.rows + 15) / 16;
@@ -2027,7 +2038,7 @@ int launch_wide_fwd(const acattn_tail_problem& p, const acattn_tail_saved& s, hi
   }
   if constexpr (H <= 128) {
   if (wide_split(p.rows))
-    hipLaunchKernelGGL((tail_wide_fwd_kernel<H, I, 4>), dim3(blocks), dim3(256), 0, stream, p, s);
+    hipLaunchKernelGGL((tail_wide_fwd_kernel<H, I, wide_fwd_waves<I>()>), dim3(blocks), dim3(64 * wide_fwd_waves<I>()), 0, stream, p, s);
   else if (per_wave)
     hipLaunchKernelGGL((tail_wide_fwd_kernel<H, I, 1>), dim3(blocks), dim3(64), 0, stream, p, s);
   else
@@ -2043,7 +2054,7 @@ int launch_wide_bwd(const acattn_tail_problem& p, const acattn_tail_saved& s, co
     return -1;
   }
   float* ws = (float*)io.workspace;
-  hipLaunchKernelGGL(tail_transpose_kernel, dim3(I / 16, I / 16, 3), dim3(256), 0, stream, p.w1, p.w2, p.wd, H, I, ws);
+  hipLaunchKernelGGL(tail_transpose_kernel, dim3(transpose_tiles<H, I>(), transpose_tiles<H, I>(), 3), dim3(256), 0, stream, p.w1, p.w2, p.wd, H, I, ws);
   const int blocks = (p.rows + 15) / 16;
   const bool split = wide_split(p.rows);
   static const bool per_wave = getenv("ACATTN_TAIL_PER_WAVE") != nullptr;  // measurement: the per-wave weight stream
@@ -2131,7 +2142,7 @@ int launch_bwd(const acattn_tail_problem& p, const acattn_tail_saved& s, const a
       return -1;
     }
     float* ws = (float*)io.workspace;
-    hipLaunchKernelGGL(tail_transpose_kernel, dim3(I / 16, I / 16, 3), dim3(256), 0, stream, p.w1, p.w2, p.wd, H, I, ws);
+    hipLaunchKernelGGL(tail_transpose_kernel, dim3(transpose_tiles<H, I>(), transpose_tiles<H, I>(), 3), dim3(256), 0, stream, p.w1, p.w2, p.wd, H, I, ws);
     const int wgs = (p.rows + 16 * NWV - 1) / (16 * NWV);
     if (s.gelu_grad)
       hipLaunchKernelGGL((tail_chunked_bwd_kernel<H, I, true>), dim3(wgs), dim3(64 * NWV), 0, stream, p, s, io, (const float*)ws);
@@ -2163,7 +2174,7 @@ int launch_bwd(const acattn_tail_problem& p, const acattn_tail_saved& s, const a
 }  // namespace
 
 bool acattn_tail_supported(int H, int I) {
-  return (H == 64 && (I == 256 || I == 128)) || (H == 128 && (I == 512 || I == 256)) || (H == 256 && I == 1024);
+  return (H == 64 && (I == 256 || I == 128)) || (H == 128 && (I == 512 || I == 256 || I == 64)) || (H == 256 && I == 1024);
 }
 
 int acattn_tail_bwd_partial_rows(int rows) { return (rows + rows_per_wave(rows) - 1) / rows_per_wave(rows); }
@@ -2205,6 +2216,7 @@ int acattn_launch_tail_fwd(const acattn_tail_problem& p, const acattn_tail_saved
   if (p.H == 64 && p.I == 128) return launch_fwd<64, 128>(p, s, stream);
   if (p.H == 128 && p.I == 512) return launch_wide_fwd<128, 512>(p, s, stream);
   if (p.H == 128 && p.I == 256) return launch_wide_fwd<128, 256>(p, s, stream);
+  if (p.H == 128 && p.I == 64) return launch_wide_fwd<128, 64>(p, s, stream);
   if (p.H == 256 && p.I == 1024) return launch_wide_fwd<256, 1024>(p, s, stream);
   acattn_set_error("layer tail: unsupported (hidden_size, inner_size)");
   return -1;
@@ -2216,6 +2228,7 @@ int acattn_launch_tail_bwd(const acattn_tail_problem& p, const acattn_tail_saved
   if (p.H == 64 && p.I == 128) return launch_bwd<64, 128>(p, s, io, stream);
   if (p.H == 128 && p.I == 512) return launch_wide_bwd<128, 512>(p, s, io, stream);
   if (p.H == 128 && p.I == 256) return launch_wide_bwd<128, 256>(p, s, io, stream);
+  if (p.H == 128 && p.I == 64) return launch_wide_bwd<128, 64>(p, s, io, stream);
   if (p.H == 256 && p.I == 1024) return launch_wide_bwd<256, 1024>(p, s, io, stream);
   acattn_set_error("layer tail: unsupported (hidden_size, inner_size)");
   return -1;

@@ -3,7 +3,8 @@
     a   = LayerNorm(dropout(dense(ctx)) + x)                  cal_adjusted_outputs, recbole/model/layers.py:681-683
     out = LayerNorm(dropout(dense_2(gelu(dense_1(a)))) + a)   FeedForward.forward,  layers.py:790-798
 
-`_FusedLayerTail` (hidden 64, inner 256 / 128: the shipped configuration): ONE HIP launch forward
+`_FusedLayerTail` ((hidden, inner) = (64, 256 / 128), (128, 512 / 256 / 64): the four shipped configurations are (64, 128) and
+(128, 64); (256, 1024) on request, see fused_supported): ONE HIP launch forward
 (acattn_layer_tail_fwd: the three products with the chain held in registers, csrc/acattn_tail.hip; at hidden 64 on bf16
 matrix instructions with exactly split operands, the weights split once per encoder forward (planes.py) or, for a node
 called on its own, once per node by acattn_layer_tail_split_weights)
@@ -23,7 +24,7 @@ import ctypes as C
 import torch
 import torch.nn.functional as F
 
-from . import _lib, fused_ln, ops
+from . import _lib, attn_launch, fused_ln, ops
 from .ops import _ptr, _stream
 from .state import state_of
 
@@ -71,7 +72,7 @@ class _FusedLayerTail(torch.autograd.Function):
         rows = 1
         for d in out_shape[:-1]:
             rows *= d
-        new = lambda *shape: torch.empty(*shape, device=c.device, dtype=torch.float32)
+        new = attn_launch.allocator(c, attn_launch.POISON)  # (NaN-filled under ACATTN_POISON_OUTPUTS=1)
         h1, a, h3, out = (new(*out_shape) for _ in range(4))
         st1, st2, act = new(rows, 2), new(rows, 2), new(rows, I)
         # hidden 128: gelu'(dense_1(a)) is saved as well (the backward would spend a fourth of its matrix work rebuilding it)
@@ -115,7 +116,7 @@ class _FusedLayerTail(torch.autograd.Function):
         need_c, need_x = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         lib = _lib.load()
         rows, H, I = act.shape[0], c.shape[-1], act.shape[-1]
-        new = lambda *shape: torch.empty(*shape, device=c.device, dtype=torch.float32)
+        new = attn_launch.allocator(c, attn_launch.POISON)  # (NaN-filled under ACATTN_POISON_OUTPUTS=1)
         d_out = d_out.contiguous()
         p = _tail_problem(c, x, *params, eps1, eps2, p1, p2, k1, k2, seed1, seed2, seed_t, pick)
         p.split_planes = _ptr(planes) if planes.numel() else None  # the forward's planes: the same products both ways

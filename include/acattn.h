@@ -432,7 +432,8 @@ int acattn_linear_wgrad_reduce_many(const float* const* part_w, const float* con
  * The position-wise tail of one branch of an encoder layer in one launch (forward) / one launch (input gradients):
  *     a   = LayerNorm(dropout(dense(ctx)) + x)                  recbole/model/layers.py:681-683 (cal_adjusted_outputs)
  *     out = LayerNorm(dropout(dense_2(gelu(dense_1(a)))) + a)   recbole/model/layers.py:790-798 (FeedForward, erf-GELU)
- * Replaces 3 GEMM + 2 dropout/add/LayerNorm + 1 GELU launches.  (H, I) in {(64, 256), (64, 128)}; weights are the
+ * Replaces 3 GEMM + 2 dropout/add/LayerNorm + 1 GELU launches.  (H, I) in {(64, 256), (64, 128), (128, 512), (128, 256),
+ * (128, 64), (256, 1024)} (acattn_layer_tail_supported); weights are the
  * row-major nn.Linear parameters ([out, in]).  Dropout decisions are those of acattn_dropout_add_layernorm_* for
  * the same (seed, row, column). */
 typedef struct acattn_tail_problem {

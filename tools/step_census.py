@@ -17,7 +17,9 @@ marks = [i for i, r in enumerate(rows) if "adam_step_kernel" in r["Kernel_Name"]
 if len(marks) < 3:
     marks = [i for i, r in enumerate(rows) if re.search(r"(^|[ :])ce_fwd_kernel<", r["Kernel_Name"])]
 spans = list(zip(marks, marks[1:]))
-mode = collections.Counter(b - a for a, b in spans).most_common(1)[0][0]
+# (spans of one launch are back-to-back Adam launches, not steps)
+lengths = collections.Counter(b - a for a, b in spans if b - a > 1) or collections.Counter(b - a for a, b in spans)
+mode = lengths.most_common(1)[0][0]
 spans = [(a, b) for a, b in spans if b - a == mode]
 steps = len(spans)
 seg = [r for a, b in spans for r in rows[a:b]]
