@@ -180,6 +180,8 @@ SYMBOLS = {
     "acattn_projections_bwd": (C.c_int, [C.POINTER(ProjProblem), C.POINTER(ProjBwdIO), C.c_void_p]),
     "acattn_layer_tail_supported": (C.c_int, [C.c_int32, C.c_int32]),
     "acattn_layer_tail_fwd": (C.c_int, [C.POINTER(TailProblem), C.POINTER(TailSaved), C.c_void_p]),
+    "acattn_layer_tail_fwd_pair": (C.c_int, [C.POINTER(TailProblem), C.POINTER(TailSaved), C.POINTER(TailProblem),
+                                            C.POINTER(TailSaved), C.c_void_p]),
     "acattn_layer_tail_bwd": (C.c_int, [C.POINTER(TailProblem), C.POINTER(TailSaved), C.POINTER(TailBwdIO), C.c_void_p]),
     "acattn_layer_tail_bwd_partial_rows": (C.c_int32, [C.c_int32]),
     "acattn_layer_tail_bwd_partial_rows_for": (C.c_int32, [C.c_int32, C.c_int32]),

@@ -387,6 +387,16 @@ int acattn_layer_tail_fwd(const acattn_tail_problem* p, const acattn_tail_saved*
   return rc;
 }
 
+int acattn_layer_tail_fwd_pair(const acattn_tail_problem* p_a, const acattn_tail_saved* saved_a, const acattn_tail_problem* p_b,
+                               const acattn_tail_saved* saved_b, void* stream) {
+  if (int rc = check_tail(p_a, saved_a)) return rc;
+  if (int rc = check_tail(p_b, saved_b)) return rc;
+  if (!saved_a->act || !saved_a->out || !saved_b->act || !saved_b->out) return fail("layer tail forward: act and out must be non-NULL");
+  const int rc = acattn_launch_tail_fwd_pair(*p_a, *saved_a, *p_b, *saved_b, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
 int acattn_layer_tail_bwd(const acattn_tail_problem* p, const acattn_tail_saved* saved, const acattn_tail_bwd_io* io,
                           void* stream) {
   if (int rc = check_tail(p, saved)) return rc;

@@ -358,6 +358,8 @@ int64_t acattn_tail_split_bytes(int H, int I, int rows);
 int acattn_launch_tail_split(const acattn_tail_problem& p, void* planes, hipStream_t stream);
 int acattn_launch_split_many(const acattn_split_layer* layers, int n_layers, hipStream_t stream);
 int acattn_launch_tail_fwd(const acattn_tail_problem& p, const acattn_tail_saved& s, hipStream_t stream);
+int acattn_launch_tail_fwd_pair(const acattn_tail_problem& pa, const acattn_tail_saved& sa, const acattn_tail_problem& pb,
+                                const acattn_tail_saved& sb, hipStream_t stream);
 int acattn_launch_tail_bwd(const acattn_tail_problem& p, const acattn_tail_saved& s, const acattn_tail_bwd_io& io,
                            hipStream_t stream);
 int64_t acattn_linear_wgrad_ws_bytes(int64_t M, int K, int N);

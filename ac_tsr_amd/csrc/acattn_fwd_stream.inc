@@ -30,6 +30,7 @@
 // Lane layout and arithmetic: S^T = K.Q^T on fp32 MFMA 16x16x4, lane (c = lane & 15, g = lane >> 4) holds query row
 // i0 + c and keys 16 t + 4 g + r; row reductions by permlane swaps; probabilities feed ctx^T = V^T.P^T directly.
 #include <stdlib.h>
+#include <string.h>
 
 #include <type_traits>
 
@@ -513,6 +514,20 @@ __device__ __forceinline__ void stream_tail_block(const acattn_problem& P, const
     const rsrc_t rM = make_rsrc(O.attack_mask + (bh * L + i0) * L, ACATTN_BYTES(5, n_blk * 4));
     if (256 * 0 < n_blk) {
       const f4 v0 = *(const f4*)(m_stage + 4 * lane);
+      if (HALF && O.penalty_part) {  // (uniform) the block's sum of (1 - M)^2, as the ordinary path forms it (penalty_late)
+        const f4 d = 1.0f - v0;
+        float pen = 0.f;
+        if (4 * lane + 4 <= n_blk) {
+          pen = (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (4 * lane + r < n_blk) pen += d[r] * d[r];
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) pen += __shfl_xor(pen, off);
+        if (lane == 0) O.penalty_part[bh * nT + qb] = pen;
+      }
       if ((n_blk & 3) == 0) {
         bstore4(rM, 16 * lane, 0, v0);
       } else {
@@ -835,15 +850,21 @@ __global__ void __launch_bounds__(64, (stream_waves<DH, NT, PRE>())) acattn_fwd_
         if (j0 + r < L) p[r] = val[r];
     }
   };
-  // (long sequences, acattn_fwd_out.penalty_part: the block's sum of (1 - M)^2 is formed from the values as they leave)
+  // (acattn_fwd_out.penalty_part: the block's sum of (1 - M)^2.  Long sequences form it from the values as they leave.
+  // L <= 64 runs at its register limit there -- the sums inside store_block cost the dh = 32 kernel 8 spilled registers --
+  // so it sums the block, which stays in LDS, at the very end of the wave, where nothing else is live: kPenaltyLate.
+  // p_drop = 0.5 only: the general-p instantiation sits at 128 registers as well and spilled 4-8 of them wherever the
+  // sums were put (inside store_block, at the end, behind a call), so its launcher leaves them to the launch behind it.)
   constexpr bool kPenalty = ADV && NT > 4;
+  constexpr bool kPenaltyLate = ADV && NT <= 4 && HALF;
+  const bool want_pen = kPenalty && O.penalty_part != nullptr;
   float pen_acc = 0.f;
   auto store_block = [&]() {
 #pragma unroll
     for (int k = 0; k < (16 * 16 * NT + 255) / 256; ++k) {
       if (256 * k < n_blk) {
         const f4 val = *(const f4*)(m_stage + 256 * k + 4 * lane);
-        if (kPenalty && O.penalty_part) {
+        if (want_pen) {
           const int o0 = 256 * k + 4 * lane;
           const f4 d = 1.0f - val;
           if (o0 + 4 <= n_blk) {
@@ -1083,7 +1104,7 @@ __global__ void __launch_bounds__(64, (stream_waves<DH, NT, PRE>())) acattn_fwd_
     }
     for (int t = nt; t < nT; ++t) stage_seg(t, f4{0.f, 0.f, 0.f, 0.f});  // skipped tiles
     store_block();
-    if (kPenalty && O.penalty_part) {
+    if (want_pen) {
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) pen_acc += __shfl_xor(pen_acc, off);
       if (lane == 0) O.penalty_part[bh * nT + qb] = pen_acc;
@@ -1166,7 +1187,7 @@ __global__ void __launch_bounds__(64, (stream_waves<DH, NT, PRE>())) acattn_fwd_
   if (ADV && !kEarlyM) {
     for (int t = nt; t < nT; ++t) stage_seg(t, f4{0.f, 0.f, 0.f, 0.f});  // skipped tiles
     store_block();  // travels under pass 3
-    if (kPenalty && O.penalty_part) {
+    if (want_pen) {
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) pen_acc += __shfl_xor(pen_acc, off);
       if (lane == 0) O.penalty_part[bh * nT + qb] = pen_acc;
@@ -1237,6 +1258,29 @@ __global__ void __launch_bounds__(64, (stream_waves<DH, NT, PRE>())) acattn_fwd_
     store_out4(sp, f4{(mx + lg2(zx)) * kLn2 + sh, (my + lg2(zy)) * kLn2 + sh, sh + fast_log(zu), sh + fast_log(zv)});
     store_out4(sp + 4, f4{sh + fast_log(zw), 0.f, 0.f, 0.f});
   }
+  if constexpr (kPenaltyLate) {
+    if (O.penalty_part) {  // (wave-uniform: a launch without it branches around the sums)
+      __builtin_amdgcn_sched_barrier(0);  // the LDS reads stay down here (hoisted into pass 3 they are spills again)
+      float pen = 0.f;
+#pragma unroll
+      for (int k = 0; k < (16 * 16 * NT + 255) / 256; ++k) {
+        if (256 * k < n_blk) {
+          const int o0 = 256 * k + 4 * lane;
+          const f4 d = 1.0f - *(const f4*)(m_stage + o0);
+          if (o0 + 4 <= n_blk) {
+            pen += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+          } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (o0 + r < n_blk) pen += d[r] * d[r];
+          }
+        }
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) pen += __shfl_xor(pen, off);
+      if (lane == 0) O.penalty_part[bh * nT + qb] = pen;
+    }
+  }
 #ifdef ACATTN_STAMPS
   ACATTN_STAMP(6);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1293,7 +1337,15 @@ int launch_stream_nt(const acattn_problem& p, const acattn_fwd_out& o, hipStream
 // pre != 0: p.affine is set (and, with the adversarial calibrator, p.gate_logits holds probabilities)
 int ACATTN_CAT(acattn_launch_fwd_stream_dh, ACATTN_STREAM_DH)(const acattn_problem& p, const acattn_fwd_out& o, int pre, hipStream_t stream) {
   constexpr int DH = ACATTN_STREAM_DH;
-  if (p.L <= 64) return pre ? launch_stream_nt<DH, 4, true>(p, o, stream) : launch_stream_nt<DH, 4, false>(p, o, stream);
-  if (p.adversarial && o.penalty_part) acattn_penalty_written_set(true);  // the 13-tile form fills it (store_block)
+  // both forms fill acattn_fwd_out.penalty_part themselves, the 4-tile form at p_drop = 0.5 only (see kPenaltyLate).
+  // ACATTN_FWD_PENALTY=separate (measurement) keeps the 4-tile form's sums in acattn_launch_penalty_rows behind the launch.
+  static const bool separate4 = getenv("ACATTN_FWD_PENALTY") && !strcmp(getenv("ACATTN_FWD_PENALTY"), "separate");
+  if (p.L <= 64) {
+    acattn_fwd_out o4 = o;
+    if (separate4 || p.p_drop != 0.5f) o4.penalty_part = nullptr;
+    if (p.adversarial && o4.penalty_part) acattn_penalty_written_set(true);
+    return pre ? launch_stream_nt<DH, 4, true>(p, o4, stream) : launch_stream_nt<DH, 4, false>(p, o4, stream);
+  }
+  if (p.adversarial && o.penalty_part) acattn_penalty_written_set(true);
   return pre ? launch_stream_nt<DH, 13, true>(p, o, stream) : launch_stream_nt<DH, 13, false>(p, o, stream);
 }

@@ -111,13 +111,14 @@ struct Rows {
   bool ok[NB];      // row < R (stores)
 };
 
+// (blk: the workgroup's row block of P -- blockIdx.x, but for a launch that covers two problems)
 template <int NB>
-__device__ __forceinline__ Rows<NB> wave_rows(const acattn_tail_problem& P) {
+__device__ __forceinline__ Rows<NB> wave_rows(const acattn_tail_problem& P, const int blk = blockIdx.x) {
   Rows<NB> w;
   const int c = threadIdx.x & 15, R = P.rows;
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
-    const int r = (blockIdx.x * NB + nb) * 16 + c;
+    const int r = (blk * NB + nb) * 16 + c;
     w.ok[nb] = r < R;
     w.row[nb] = r < R ? r : R - 1;
     // gather and tail commute (the tail is position-wise): the positions the model reads are picked here instead of
@@ -729,15 +730,16 @@ __device__ __forceinline__ void split_square(const b8* mat, int lane, const b8 (
 }
 
 // NB, NW and the row blocks as tail_fwd_kernel; wave `wave` of NW takes the slab pairs wave, wave + NW, ...
-template <int H, int I, int NB, int NW = 1>
-__global__ void __launch_bounds__(64 * NW) tail_split_fwd_kernel(const acattn_tail_problem P, const acattn_tail_saved S) {
+// (the body of tail_split_fwd_kernel and tail_split_fwd_pair_kernel for the workgroup's row block `blk` of problem P)
+template <int H, int I, int NB, int NW>
+__device__ __forceinline__ void tail_split_fwd_block(const acattn_tail_problem& P, const acattn_tail_saved& S, const int blk) {
   static_assert(H == 64 && (NW == 1 || NB == 1), "hidden 64; the slab split works on one row block");
   using L = TailPlanes<I>;
   constexpr int DT = 4, NP = I / 32, NJ = NP / NW;  // slab pairs, per wave
   static_assert(NP % NW == 0 && NJ >= 1, "whole pairs per wave");
   const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
   const int wave = NW > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
-  const Rows<NB> W = wave_rows<NB>(P);
+  const Rows<NB> W = wave_rows<NB>(P, blk);
   const uint64_t step = P.seed_device ? *P.seed_device : 0ull;
   const b8* planes = (const b8*)P.split_planes;
   const b8 *pw1 = planes + L::FWD_1, *pw2 = planes + L::FWD_2;
@@ -882,6 +884,28 @@ __global__ void __launch_bounds__(64 * NW) tail_split_fwd_kernel(const acattn_ta
       if (g == 0) *(float2*)(S.st2 + 2 * (size_t)W.row[nb]) = float2{mean, rstd};
     }
   }
+}
+
+template <int H, int I, int NB, int NW = 1>
+__global__ void __launch_bounds__(64 * NW) tail_split_fwd_kernel(const acattn_tail_problem P, const acattn_tail_saved S) {
+  tail_split_fwd_block<H, I, NB, NW>(P, S, blockIdx.x);
+}
+
+// Two problems of the same shape in ONE launch of the four-wave form (the attacked and the calibrated tail of the last
+// layer: 32 workgroups each at 512 rows, a latency chain on their own): workgroups [0, blocks) are problem a's, the others
+// problem b's -- a workgroup-uniform choice, and behind it tail_split_fwd_kernel's arithmetic on that problem.
+struct TailPair {
+  acattn_tail_problem pa, pb;
+  acattn_tail_saved sa, sb;
+  int blocks;
+};
+
+template <int H, int I>
+__global__ void __launch_bounds__(256) tail_split_fwd_pair_kernel(const TailPair A) {
+  const bool second = (int)blockIdx.x >= A.blocks;  // (uniform)
+  const acattn_tail_problem P = second ? A.pb : A.pa;
+  const acattn_tail_saved S = second ? A.sb : A.sa;
+  tail_split_fwd_block<H, I, 1, 4>(P, S, second ? blockIdx.x - A.blocks : blockIdx.x);
 }
 
 template <int H, int I, int NB, int NW = 1>
@@ -2220,6 +2244,22 @@ int acattn_launch_tail_fwd(const acattn_tail_problem& p, const acattn_tail_saved
   if (p.H == 256 && p.I == 1024) return launch_wide_fwd<256, 1024>(p, s, stream);
   acattn_set_error("layer tail: unsupported (hidden_size, inner_size)");
   return -1;
+}
+
+// -100: the two problems do not both take the four-wave split form (the caller launches them one by one)
+int acattn_launch_tail_fwd_pair(const acattn_tail_problem& pa, const acattn_tail_saved& sa, const acattn_tail_problem& pb,
+                                const acattn_tail_saved& sb, hipStream_t stream) {
+  if (pa.H != 64 || pb.H != 64 || pa.I != pb.I || (pa.I != 256 && pa.I != 128) || pa.rows != pb.rows) return -100;
+  if (!pa.split_planes || !pb.split_planes || !tail_split_products(64, pa.I, pa.rows)) return -100;
+  if (rows_per_wave(pa.rows) != 16 || !split_slabs(pa.rows)) return -100;
+  TailPair A;
+  A.pa = pa, A.pb = pb, A.sa = sa, A.sb = sb;
+  A.blocks = (pa.rows + 15) / 16;
+  if (pa.I == 256)
+    hipLaunchKernelGGL((tail_split_fwd_pair_kernel<64, 256>), dim3(2 * A.blocks), dim3(256), 0, stream, A);
+  else
+    hipLaunchKernelGGL((tail_split_fwd_pair_kernel<64, 128>), dim3(2 * A.blocks), dim3(256), 0, stream, A);
+  return (int)hipGetLastError();
 }
 
 int acattn_launch_tail_bwd(const acattn_tail_problem& p, const acattn_tail_saved& s, const acattn_tail_bwd_io& io,

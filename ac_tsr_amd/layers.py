@@ -228,11 +228,24 @@ class AttackRTransformerLayer(nn.Module):
             return self.feed_forward(att.output(ctx_layer, residual, keep_out), keep_ffn)
 
         attacked_feedforward_output = None
-        if _need_attacked:
-            attacked_feedforward_output = branch(ctx_att, getattr(_rnd, "keep_out_att", None),
-                                                 getattr(_rnd, "keep_ffn_att", None))
-        calibrated_feedforward_output = branch(ctx_cal, getattr(_rnd, "keep_out_cal", None),
-                                               getattr(_rnd, "keep_ffn_cal", None))
+        if (_need_attacked and ctx_cal.is_cuda and tail.supported(att, self.feed_forward)
+                and tail.fused_supported(att, self.feed_forward)):
+            # both branches take the single-launch tail on the same rows: one forward launch for the two where the library
+            # has a pair form (the last layer's picked rows), the same two nodes either way
+            keeps_att = (pick(getattr(_rnd, "keep_out_att", None)), pick(getattr(_rnd, "keep_ffn_att", None)))
+            keeps_cal = (pick(getattr(_rnd, "keep_out_cal", None)), pick(getattr(_rnd, "keep_ffn_cal", None)))
+            if _rows is not None:
+                attacked_feedforward_output, calibrated_feedforward_output = tail.layer_tail_pair(
+                    ctx_att, ctx_cal, hidden_res, att, self.feed_forward, keeps_att, keeps_cal, pick=_rows, planes=_planes)
+            else:
+                attacked_feedforward_output, calibrated_feedforward_output = tail.layer_tail_pair(
+                    ctx_att, ctx_cal, residual, att, self.feed_forward, keeps_att, keeps_cal, planes=_planes)
+        else:
+            if _need_attacked:
+                attacked_feedforward_output = branch(ctx_att, getattr(_rnd, "keep_out_att", None),
+                                                     getattr(_rnd, "keep_ffn_att", None))
+            calibrated_feedforward_output = branch(ctx_cal, getattr(_rnd, "keep_out_cal", None),
+                                                   getattr(_rnd, "keep_ffn_cal", None))
         combined_attention_prob = probs.get("calibrated_attention")
         if return_all_attention_prob:
             all_attention_prob = {

@@ -20,6 +20,7 @@ instead of six autograd nodes with their own reductions and the elementwise adds
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import torch
 import torch.nn.functional as F
@@ -31,6 +32,9 @@ from .state import state_of
 # measurement switch (bench.py --tail unfused): route supported sizes through the unfused node as well
 FUSED_KERNEL = True
 FUSED_MAX_HIDDEN = 128  # widest hidden size routed to the single-launch node by default (256 is supported, see fused_supported)
+# The attacked and the calibrated tail of a layer in ONE forward launch (layer_tail_pair, acattn_layer_tail_fwd_pair) where
+# that applies; ACATTN_TAIL_PAIRED=0 keeps the two launches (A/B runs, tests).
+PAIRED_FORWARD = os.environ.get("ACATTN_TAIL_PAIRED", "1") != "0"
 
 
 def _tail_problem(c, x, wd, bd, g1, b1, w1, bb1, w2, bb2, g2, b2, eps1, eps2, p1, p2, k1, k2, seed1, seed2, seed_t,
@@ -53,10 +57,11 @@ def _tail_problem(c, x, wd, bd, g1, b1, w1, bb1, w2, bb2, g2, b2, eps1, eps2, p1
 class _FusedLayerTail(torch.autograd.Function):
     @staticmethod
     def forward(ctx, c, x, wd, bd, g1, b1, w1, bb1, w2, bb2, g2, b2, eps1, eps2, p1, p2, keep1, keep2, seed1, seed2,
-                seed_tensor, state, pick=None, shared=None):
+                seed_tensor, state, pick=None, shared=None, done=None):
         """`pick` ([B, R] int64 positions): the tail runs on those positions of c / x ([B, L, H]) only and returns
         [B, R, H]; explicit keep masks are then [B, R, H] as well.  `shared` (planes.LayerPlanes or None): the weight
-        planes the encoder made for this forward; without them the node splits the weights itself."""
+        planes the encoder made for this forward; without them the node splits the weights itself.  `done` (layer_tail_pair):
+        the forward launch has run -- (h1, st1, a, act, h3, st2, out) as this node would have allocated and filled them."""
         ctx.state = state
         c, x = c.contiguous(), x.contiguous()
         params = tuple(t.contiguous() for t in (wd, bd, g1, b1, w1, bb1, w2, bb2, g2, b2))
@@ -72,6 +77,16 @@ class _FusedLayerTail(torch.autograd.Function):
         rows = 1
         for d in out_shape[:-1]:
             rows *= d
+        if done is not None:  # paired launch (hidden 64 on the encoder's planes): nothing left to compute
+            h1, st1, a, act, h3, st2, out = done
+            ctx.shared = shared
+            empty = c.new_empty(0)
+            ctx.save_for_backward(c, x, h1, st1, a, act, h3, st2, *params, k1 if k1 is not None else empty,
+                                  k2 if k2 is not None else empty, seed_tensor if seed_tensor is not None else empty,
+                                  pick if pick is not None else empty, empty, empty)
+            ctx.args = (eps1, eps2, p1, p2, k1 is not None, k2 is not None, seed1, seed2, seed_tensor is not None,
+                        pick is not None)
+            return out
         new = attn_launch.allocator(c, attn_launch.POISON)  # (NaN-filled under ACATTN_POISON_OUTPUTS=1)
         h1, a, h3, out = (new(*out_shape) for _ in range(4))
         st1, st2, act = new(rows, 2), new(rows, 2), new(rows, I)
@@ -152,7 +167,7 @@ class _FusedLayerTail(torch.autograd.Function):
             gb = ops.sum_rows0(part, ctx.state).view(4, H)  # (dgamma1, dbeta1, dgamma2, dbeta2)
             grads = [gwd, gbd, gb[0], gb[1], gw1, gb1, gw2, gb2, gb[2], gb[3]]
             ctx.state.watch(gb, grads[2], grads[3], grads[8], grads[9])
-        return (d_c, d_x, *grads, None, None, None, None, None, None, None, None, None, None, None, None)
+        return (d_c, d_x, *grads, None, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
 
@@ -217,6 +232,77 @@ def fused_supported(att, ffn) -> bool:
     if H > FUSED_MAX_HIDDEN:
         return False
     return FUSED_KERNEL and bool(_lib.load().acattn_layer_tail_supported(H, ffn.dense_1.out_features))
+
+
+def _pair_forward(c_a, c_b, x, params, eps1, eps2, p1, p2, keeps_a, keeps_b, seeds_a, seeds_b, seed_t, pick, shared):
+    """Both branches' forward launch as one (acattn_layer_tail_fwd_pair), not recorded by autograd: per branch the tensors
+    _FusedLayerTail.forward allocates and fills, or None where the pair form does not apply."""
+    H, I = c_a.shape[-1], params[4].shape[0]
+    if H != 64 or shared is None or shared.tail is None or c_a.shape != c_b.shape:
+        return None
+    lib = _lib.load()
+    out_shape = (*pick.shape, H) if pick is not None else c_a.shape
+    rows = 1
+    for d in out_shape[:-1]:
+        rows *= d
+    nbytes = int(lib.acattn_layer_tail_split_bytes(H, I, rows))
+    if nbytes <= 0 or shared.tail.numel() * 4 != nbytes:
+        return None
+    with torch.no_grad():
+        x = x.detach().contiguous()
+        params = tuple(t.detach().contiguous() for t in params)
+        pick = None if pick is None else pick.contiguous()
+        keep = lambda k: None if k is None else k.to(torch.uint8).contiguous()
+        sides = []
+        for c, keeps, seeds in ((c_a, keeps_a, seeds_a), (c_b, keeps_b, seeds_b)):
+            c = c.detach().contiguous()
+            new = attn_launch.allocator(c, attn_launch.POISON)
+            h1, a, h3, out = (new(*out_shape) for _ in range(4))
+            st1, st2, act = new(rows, 2), new(rows, 2), new(rows, I)
+            k1, k2 = keep(keeps[0]), keep(keeps[1])
+            p = _tail_problem(c, x, *params, eps1, eps2, p1, p2, k1, k2, seeds[0], seeds[1], seed_t, pick)
+            p.split_planes = _ptr(shared.tail)
+            sv = _lib.TailSaved()
+            sv.h1, sv.st1, sv.a, sv.act, sv.h3, sv.st2, sv.out = (_ptr(t) for t in (h1, st1, a, act, h3, st2, out))
+            sides.append((p, sv, (h1, st1, a, act, h3, st2, out), (c, k1, k2)))
+        (pa, sa, done_a, _), (pb, sb, done_b, _) = sides
+        rc = lib.acattn_layer_tail_fwd_pair(C.byref(pa), C.byref(sa), C.byref(pb), C.byref(sb), _stream())
+        if rc == -100:
+            return None
+        _lib.check(rc, "layer_tail_fwd_pair")
+    return done_a, done_b
+
+
+def layer_tail_pair(ctx_a, ctx_b, input_tensor, att, ffn, keeps_a=(None, None), keeps_b=(None, None), pick=None, planes=None):
+    """(layer_tail(ctx_a, ...), layer_tail(ctx_b, ...)) -- the attacked and the calibrated branch of one layer, each with its
+    own (keep_out, keep_ffn) -- with ONE forward launch for both where the fused node's four-wave hidden-64 form takes
+    them (acattn_layer_tail_fwd_pair): the same two autograd nodes, the same seeds in the same order, the same bits."""
+    if not (PAIRED_FORWARD and fused_supported(att, ffn) and ctx_a.is_cuda and ctx_a.dtype == torch.float32):
+        return (layer_tail(ctx_a, input_tensor, att, ffn, *keeps_a, pick=pick, planes=planes),
+                layer_tail(ctx_b, input_tensor, att, ffn, *keeps_b, pick=pick, planes=planes))
+    state = state_of(att)
+    training = att.training
+    seeds, ps = [], []
+    for keep_out, keep_ffn in (keeps_a, keeps_b):  # (the draws of two layer_tail calls, in their order)
+        p1 = att.out_dropout.p if (training or keep_out is not None) else 0.0
+        p2 = ffn.dropout.p if (training or keep_ffn is not None) else 0.0
+        seeds.append((state.draw_seed() if (p1 > 0 and keep_out is None) else 0,
+                      state.draw_seed() if (p2 > 0 and keep_ffn is None) else 0))
+        ps.append((p1, p2))
+    seed_ts = [state.seed_tensor if (k[0] is None and k[1] is None) else None for k in (keeps_a, keeps_b)]
+    params = (att.dense.weight, att.dense.bias, att.LayerNorm.weight, att.LayerNorm.bias, ffn.dense_1.weight, ffn.dense_1.bias,
+              ffn.dense_2.weight, ffn.dense_2.bias, ffn.LayerNorm.weight, ffn.LayerNorm.bias)
+    eps1, eps2 = att.LayerNorm.eps, ffn.LayerNorm.eps
+    done = None
+    # (the training forward only: under no_grad no node is recorded and an inference forward keeps its two single launches)
+    if torch.is_grad_enabled() and ps[0] == ps[1] and seed_ts[0] is seed_ts[1]:
+        done = _pair_forward(ctx_a, ctx_b, input_tensor, params, eps1, eps2, *ps[0], keeps_a, keeps_b, seeds[0], seeds[1],
+                             seed_ts[0], pick, planes)
+    outs = []
+    for k, (c, keeps) in enumerate(((ctx_a, keeps_a), (ctx_b, keeps_b))):
+        outs.append(_FusedLayerTail.apply(c, input_tensor, *params, eps1, eps2, *ps[k], *keeps, *seeds[k], seed_ts[k], state,
+                                          pick, planes, None if done is None else done[k]))
+    return outs[0], outs[1]
 
 
 def layer_tail(ctx_layer, input_tensor, att, ffn, keep_out=None, keep_ffn=None, pick=None, planes=None):

@@ -121,9 +121,9 @@ typedef struct acattn_fwd_out {
   float* perturbed_attention;
   float* calibrated_attention;
   /* ABI 26, optional (adversarial form only): [B, nh, ceil(L/16)] -- acattn_mask_penalty_rows of attack_mask, i.e.
-   * sum (1 - M)^2 over each query block's rows and all L keys.  The long-sequence streaming forward forms the sums from
-   * the M block it stages for its store; for every other kernel the entry point runs acattn_mask_penalty_rows behind the
-   * launch.  Always filled when given. */
+   * sum (1 - M)^2 over each query block's rows and all L keys.  The streaming forward (L > 64; L <= 64 at p_drop = 0.5) sums the
+   * M block it stages for its store; for every other kernel the entry point runs acattn_mask_penalty_rows behind the
+   * launch.  Always filled when given; the two ways differ in the order of the sum only. */
   float* penalty_part;
 } acattn_fwd_out;
 
@@ -501,6 +501,14 @@ typedef struct acattn_tail_bwd_io {
 
 int acattn_layer_tail_supported(int32_t H, int32_t I);
 int acattn_layer_tail_fwd(const acattn_tail_problem* p, const acattn_tail_saved* saved, void* stream);
+/* [added within ABI 34: a new entry point, nothing existing changes] acattn_layer_tail_fwd(p_a, saved_a) and
+ * acattn_layer_tail_fwd(p_b, saved_b) as ONE launch of twice the workgroups: the attacked and the calibrated tail of a
+ * layer -- the same weights and planes, each with its own ctx, outputs, saved tensors and dropout seeds.  Every output is
+ * bit for bit what the two single launches write.  Returns -100 (no error text) where the pair form does not apply --
+ * hidden size other than 64, different inner sizes or row counts, no split planes, a row count that does not take the
+ * four-wave form -- and the caller makes the two calls. */
+int acattn_layer_tail_fwd_pair(const acattn_tail_problem* p_a, const acattn_tail_saved* saved_a, const acattn_tail_problem* p_b,
+                               const acattn_tail_saved* saved_b, void* stream);
 int acattn_layer_tail_bwd(const acattn_tail_problem* p, const acattn_tail_saved* saved, const acattn_tail_bwd_io* io,
                           void* stream);
 int32_t acattn_layer_tail_bwd_partial_rows(int32_t rows);               /* hidden 64 */
