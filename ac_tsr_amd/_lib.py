@@ -22,8 +22,8 @@ MASK_STRUCTURED, MASK_DENSE_LL, MASK_DENSE_L = 0, 1, 2
 COMBINE = {"fixed": 0, "gate": 1, "annealing": 2}
 RICH = {"none": 0, "fixed": 1, "trainable": 2}
 RNG_EXPLICIT, RNG_COUNTER = 0, 1
-FWD_AUTO, FWD_STREAM, FWD_STAGED, FWD_GENERAL = 0, 1, 2, 3
-BWD_AUTO, BWD_STREAM, BWD_ROW = 0, 1, 2
+FWD_AUTO, FWD_STREAM, FWD_STAGED, FWD_GENERAL, FWD_LONG = 0, 1, 2, 3, 4
+BWD_AUTO, BWD_STREAM, BWD_ROW, BWD_LONG = 0, 1, 2, 3
 
 _f = C.c_void_p  # every device pointer travels as an integer address
 
@@ -151,6 +151,7 @@ SUMROWS_MAX_DEFER = 8
 # name -> (restype, argtypes); must list every symbol include/acattn.h declares (tests check this)
 SYMBOLS = {
     "acattn_abi_version": (C.c_int, []),
+    "acattn_max_sequence_length": (C.c_int, []),
     "acattn_calibrated_attention_bwd_gate_summed": (C.c_int, [C.POINTER(Problem), C.POINTER(BwdIO)]),
     "acattn_calibrated_attention_bwd_pair_supported": (C.c_int, [C.POINTER(Problem), C.POINTER(BwdIO)]),
     "acattn_last_error": (C.c_char_p, []),

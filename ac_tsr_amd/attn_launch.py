@@ -40,6 +40,14 @@ def allocator(like: torch.Tensor, poison: bool):
     return lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
 
 
+def check_sequence_length(L: int) -> None:
+    """One early, readable error for a sequence the attention core does not take (acattn_max_sequence_length(): 496)."""
+    top = _lib.load().acattn_max_sequence_length()
+    if L > top:
+        raise ValueError(f"sequence length {L} is beyond the attention core's limit of {top} "
+                         "(MAX_ITEM_LIST_LENGTH <= acattn_max_sequence_length())")
+
+
 def fill_problem(q, k, v, qa, ka, gate, w_order, b_order, w_dist, b_dist, scalar, n_heads, p_drop, seed, seed_tensor, *,
                  key_valid=None, causal=True, mask=None, mask_mode=_lib.MASK_STRUCTURED, adversarial=True, combine="gate",
                  gate_is_prob=False, affine=None, two_level=True, rich="none", rich_ratio=None, anneal_rate=0.0,
@@ -48,6 +56,7 @@ def fill_problem(q, k, v, qa, ka, gate, w_order, b_order, w_dist, b_dist, scalar
     two_level).  `rnd` = (noise, keep_after, keep_mask, keep_before), fp32 / uint8 tensors or None, selects explicit
     randomness; the caller keeps those tensors alive until the launch has returned."""
     B, L, H = q.shape
+    check_sequence_length(L)
     p = _lib.Problem()
     p.B, p.L, p.H, p.n_heads = B, L, H, n_heads
     p.q, p.k, p.v = _ptr(q), _ptr(k), _ptr(v)
@@ -105,7 +114,7 @@ def unpack_partials(tot, dh: int, w_order, b_order, w_dist, b_dist, scalar, rich
 
 
 def workspace(n_bytes: int, device) -> torch.Tensor:
-    """A launch's scratch (row scalars of the streaming backward); `n_bytes` is the library's `*_workspace_bytes` answer."""
+    """A launch's scratch (row scalars of the streaming and the long backward); `n_bytes` is the library's `*_workspace_bytes` answer."""
     return torch.empty(max(int(n_bytes), 4) // 4, device=device, dtype=torch.float32)
 
 
@@ -219,7 +228,7 @@ def attention_bwd_launch(lib, prob, q, n_heads: int, M, stats, *, d_att=None, d_
         dgate_part = rest(B, 1 if summed else n_heads, L, L)
         io.dgate_logits, io.dgate_summed = _ptr(dgate_part), int(summed)
     if second is not None and not lib.acattn_calibrated_attention_bwd_pair_supported(C.byref(prob), C.byref(io)):
-        return None  # (L <= 64: the row-resident kernel; head size 128; a pinned kernel)
+        return None  # (L <= 64: the row-resident kernel; L > 208: the long form; head size 128; a pinned kernel)
     _lib.check(lib.acattn_calibrated_attention_bwd(C.byref(prob), C.byref(io), _stream()), "calibrated_attention_bwd")
     return (dq, dk, dv, dqa, dka, dgate_part, part) + extra
 

@@ -9,6 +9,9 @@
 
 namespace {
 thread_local char g_err[256] = "";
+// 31 key tiles of 16: the long forms (acattn_long_fwd.inc, acattn_long_bwd.inc) loop over tiles at run time and would take
+// more; the ceiling is this validation's alone
+constexpr int ACATTN_MAX_L = 496;
 
 int fail(const char* msg) {
   snprintf(g_err, sizeof(g_err), "%s", msg);
@@ -22,7 +25,7 @@ int check_problem(const acattn_problem* p) {
     return fail("The hidden size is not a multiple of the number of attention heads");  // layers.py:618-622
   const int dh = p->H / p->n_heads;
   if (dh != 16 && dh != 32 && dh != 64 && dh != 128) return fail("unsupported head size: dh must be 16, 32, 64 or 128");
-  if (p->L > 208) return fail("unsupported sequence length: L must be <= 208");
+  if (p->L > ACATTN_MAX_L) return fail("unsupported sequence length: L must be <= 496 (acattn_max_sequence_length)");
   if (!p->q || !p->k || !p->v) return fail("q, k, v must be non-NULL");
   if (p->mask_mode == ACATTN_MASK_STRUCTURED) {
     if (!p->key_valid) return fail("structured mask needs key_valid");
@@ -64,6 +67,8 @@ extern "C" {
 
 int acattn_abi_version(void) { return ACATTN_ABI_VERSION; }
 
+int acattn_max_sequence_length(void) { return ACATTN_MAX_L; }
+
 int acattn_select_forward_kernel(int which) { return acattn_fwd_kernel_choice(which); }
 
 int acattn_select_backward_kernel(int which) { return acattn_bwd_kernel_choice(which); }
@@ -88,8 +93,8 @@ int acattn_calibrated_attention_fwd(const acattn_problem* p, const acattn_fwd_ou
     return fail("adversarial forward needs ctx_attacked and attack_mask outputs");
   acattn_penalty_written_set(false);
   int rc = acattn_launch_fwd(*p, *out, (hipStream_t)stream);
-  // acattn_fwd_out.penalty_part: the long-sequence streaming kernel has formed the sums itself; behind every other kernel
-  // they are taken from the mask it wrote
+  // acattn_fwd_out.penalty_part: the streaming kernel (L > 64) has formed the sums itself; behind every other kernel,
+  // the long form (L > 208) included, they are taken from the mask it wrote
   if (rc == 0 && p->adversarial && out->penalty_part && !acattn_penalty_written())
     rc = acattn_launch_penalty_rows(out->attack_mask, p->B, p->n_heads, p->L, out->penalty_part, (hipStream_t)stream);
   if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -133,12 +138,16 @@ int acattn_calibrated_attention_bwd_pair_supported(const acattn_problem* p, cons
 
 int64_t acattn_calibrated_attention_bwd_workspace_bytes(const acattn_problem* p) {
   if (!p || p->B < 1 || p->L < 1 || p->n_heads < 1) return -1;
-  return acattn_bwd_stream_ws_bytes(*p);
+  // the streaming pair keeps 8 floats per (sequence, head, row): unchanged wherever it runs.  The long form (L > 208, or
+  // pinned by the calling thread at any L) keeps 16: its row scalars and the corrections of a fully masked row's normalisers
+  const bool long_form = p->L > 208 || acattn_bwd_kernel_choice(-1) == ACATTN_BWD_LONG;
+  return (long_form ? 2 : 1) * acattn_bwd_stream_ws_bytes(*p);
 }
 
 int acattn_spatial_attention_bwd(const acattn_problem* p, const acattn_spatial_bwd_io* io, void* stream) {
   if (int rc = check_problem(p)) return rc;
   if (!io) return fail("io is NULL");
+  if (p->L > 208) return fail("the spatial-only backward is built for sequence length L <= 208 (the long form covers the forward and acattn_calibrated_attention_bwd)");
   if (p->adversarial) return fail("the spatial-only backward needs adversarial == 0 (use acattn_calibrated_attention_bwd)");
   if (!io->d_ctx) return fail("d_ctx must be non-NULL");
   if (!io->dq || !io->dk || !io->dv) return fail("dq, dk, dv must be non-NULL");

@@ -12,6 +12,7 @@ int acattn_launch_bwd_general_dh128(const acattn_problem& p, const acattn_bwd_io
 int acattn_launch_bwd_fast(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream);
 int acattn_launch_bwd_stream(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream);
 int acattn_launch_bwd_onerow(const acattn_problem& p, const acattn_bwd_io& io, bool accumulate, hipStream_t stream);
+int acattn_launch_bwd_long(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream);  // acattn_long_bwd.hip
 
 namespace {
 // per host thread: a measurement / test hook must not race with launches another thread issues
@@ -19,7 +20,7 @@ thread_local int g_bwd_kernel = ACATTN_BWD_AUTO;
 }
 int acattn_bwd_kernel_choice(int which) {
   const int old = g_bwd_kernel;
-  if (which >= ACATTN_BWD_AUTO && which <= ACATTN_BWD_ROW) g_bwd_kernel = which;
+  if (which >= ACATTN_BWD_AUTO && which <= ACATTN_BWD_LONG) g_bwd_kernel = which;
   return old;
 }
 
@@ -54,6 +55,14 @@ bool acattn_bwd_pair_supported(const acattn_problem& p, const acattn_bwd_io& io)
 }
 
 int acattn_launch_bwd(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream) {
+  // the long form (acattn_long_bwd.inc; run-time tile loops, a key-flag table in LDS): the automatic choice beyond the 208
+  // keys the kernels below are built for, at any L when pinned (ACATTN_BWD_LONG)
+  if (g_bwd_kernel == ACATTN_BWD_LONG || (g_bwd_kernel == ACATTN_BWD_AUTO && p.L > 208))
+    return acattn_launch_bwd_long(p, io, stream);
+  if (p.L > 208) {
+    acattn_set_error("backward: the pinned kernel is built for L <= 208; L > 208 needs ACATTN_BWD_LONG or ACATTN_BWD_AUTO");
+    return -1;
+  }
   if ((io.dqa2 || io.dka2 || io.d_ctx_calibrated2 || io.d_penalty_part2) && !acattn_bwd_pair_supported(p, io)) {
     acattn_set_error("attention backward: a second cotangent set was given but this launch cannot evaluate it "
                      "(ask acattn_calibrated_attention_bwd_pair_supported first)");

@@ -36,6 +36,7 @@ __global__ void acattn_rng_kernel(int B, int nh, int L, uint64_t seed, float p_d
 int acattn_launch_fwd_fast(const acattn_problem& p, const acattn_fwd_out& o, hipStream_t stream);
 int acattn_launch_fwd_dma(const acattn_problem& p, const acattn_fwd_out& o, hipStream_t stream);
 int acattn_launch_fwd_stream(const acattn_problem& p, const acattn_fwd_out& o, hipStream_t stream);
+int acattn_launch_fwd_long(const acattn_problem& p, const acattn_fwd_out& o, hipStream_t stream);  // acattn_long_fwd.hip
 
 namespace {
 // per host thread: a measurement / test hook must not race with launches another thread issues
@@ -43,7 +44,7 @@ thread_local int g_fwd_kernel = ACATTN_FWD_AUTO;
 }
 int acattn_fwd_kernel_choice(int which) {
   const int old = g_fwd_kernel;
-  if (which >= ACATTN_FWD_AUTO && which <= ACATTN_FWD_GENERAL) g_fwd_kernel = which;
+  if (which >= ACATTN_FWD_AUTO && which <= ACATTN_FWD_LONG) g_fwd_kernel = which;
   return old;
 }
 
@@ -53,7 +54,15 @@ int acattn_launch_fwd(const acattn_problem& p, const acattn_fwd_out& o, hipStrea
   //   every measured shape (B = 512: L = 50 20.8 us against 21.8 staged and 33.3 general; L = 200, H = 64: 179 us
   //   against 536 general);
   //   LDS-staged kernels (L <= 64; LDS-DMA staging for 48 < L, register staging below): ACATTN_FWD_STAGED
+  //   long form (acattn_long_fwd.inc; key tiles in a run-time loop, three sweeps): every L up to
+  //   acattn_max_sequence_length(); the automatic choice beyond the 13 key tiles the kernels above hold in registers,
+  //   at any L when pinned (ACATTN_FWD_LONG)
   const int which = g_fwd_kernel;
+  if (which == ACATTN_FWD_LONG || (which == ACATTN_FWD_AUTO && p.L > 208)) return acattn_launch_fwd_long(p, o, stream);
+  if (p.L > 208) {
+    acattn_set_error("forward: the pinned kernel holds at most 208 keys of a row; L > 208 needs ACATTN_FWD_LONG or ACATTN_FWD_AUTO");
+    return -1;
+  }
   if (which != ACATTN_FWD_GENERAL) {
     if (which == ACATTN_FWD_AUTO || which == ACATTN_FWD_STREAM) {
       const int rc_stream = acattn_launch_fwd_stream(p, o, stream);

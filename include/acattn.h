@@ -17,7 +17,12 @@
  *     positive = hipError_t from the launch.
  *
  * Shapes: B batch, L sequence length, H hidden size, nh heads, dh = H / nh.
- * Supported: dh in {16, 32, 64, 128}, 1 <= L <= 208.
+ * Supported: dh in {16, 32, 64, 128}, 1 <= L <= 496 (acattn_max_sequence_length()).  L <= 208 runs the kernels that hold a
+ * query block's row of 13 key tiles in registers; 208 < L <= 496 runs the long forms (ACATTN_FWD_LONG / ACATTN_BWD_LONG:
+ * key tiles in a run-time loop), which refuse, with an error text that names the option: two_level == 0, the four
+ * optional probability dumps of acattn_fwd_out, and in the backward dgate_summed, the second cotangent set (dqa2 ...) and a
+ * NULL workspace, and p_drop > 0.95 (their calibrated soft-max takes a fixed shift: its arguments reach e / (1 - p_drop), and
+ * exp overflows fp32 from p_drop = 0.967 on).  acattn_spatial_attention_bwd stays at L <= 208.
  */
 #ifndef ACATTN_H_
 #define ACATTN_H_
@@ -108,8 +113,10 @@ typedef struct acattn_problem {
  * ka, the attack-mask rows) that row feeds, in every forward kernel -- the streaming kernel's translation units are built with
  * -fno-honor-nans (no canonicalising v_max in front of the row maxima), which does not change that
  * (tests/test_hip_onehop.py::test_a_nan_in_the_inputs_reaches_the_outputs_of_the_streaming_forward).  Rows of PADDED positions
- * (key_valid == 0) are never read by a masked soft-max here, whereas the reference's additive -10000 would propagate a NaN
- * sitting there. */
+ * (key_valid == 0) are never read by a masked soft-max in the kernels for L <= 208, whereas the reference's additive -10000
+ * would propagate a NaN sitting there.  The long forms (ACATTN_FWD_LONG / ACATTN_BWD_LONG, every L > 208) ADD the mask as
+ * the reference does: they read K, Ka and V of padded keys inside the key tiles they visit and give them a weight of zero, so
+ * a NaN or Inf at a padded position reaches the outputs of the query blocks that visit its tile, as in the reference. */
 typedef struct acattn_fwd_out {
   float* ctx_attacked;   /* [B,L,H] head-merged perturbed_attention . V        layers.py:677-680 via :938 */
   float* ctx_calibrated; /* [B,L,H] head-merged combined attention . V         layers.py:677-680 via :942 */
@@ -157,9 +164,11 @@ typedef struct acattn_bwd_io {
   int32_t attack_only;  /* non-zero: the caller will read ONLY dqa and dka (pass 2 of the two-pass trainer through a
                            layer with no attack transform upstream, recbole/trainer/trainer.py:678-684); every other
                            output buffer must still be valid memory but may be left unwritten.  A hint like the above. */
-  void* workspace;      /* optional device scratch of acattn_calibrated_attention_bwd_workspace_bytes(p) bytes (contents
-                           irrelevant).  With it, long sequences (L > 64) take the streaming two-kernel backward
-                           (acattn_bwd_stream.hip); NULL = the row-resident kernels only. */
+  void* workspace;      /* device scratch of acattn_calibrated_attention_bwd_workspace_bytes(p) bytes (contents irrelevant;
+                           8 floats per (b, head, query row) for the streaming pair, 16 where the long form runs: L > 208,
+                           or ACATTN_BWD_LONG pinned by the thread that asks).  Optional for L <= 208: with it, L > 64
+                           takes the streaming two-kernel backward (acattn_bwd_stream.hip), NULL = the row-resident
+                           kernels only.  REQUIRED by the long form: NULL there is an error. */
   const int64_t* read_rows; /* the same hint as active_qblocks in its raw form: [B, n_read_rows] positions whose context
                            cotangents are the only non-zero ones (item_seq_len - 1 of abstract_recommender.py:130-134).
                            Consulted when active_qblocks is NULL; NULL = all active.  PRECONDITION: 0 <= position < L
@@ -739,18 +748,30 @@ int acattn_rng_materialize(int32_t B, int32_t n_heads, int32_t L, uint64_t seed,
  * and the automatic choice applies.  Returns the previous setting.  The setting is PER HOST THREAD (thread_local): it
  * affects the launches the calling thread issues afterwards and nobody else's. */
 enum {
-  ACATTN_FWD_AUTO = 0,    /* streaming kernel where it applies (training configuration, L <= 208), else general */
+  ACATTN_FWD_AUTO = 0,    /* L <= 208: streaming kernel where it applies (training configuration), else general;
+                             L > 208: the long form */
   ACATTN_FWD_STREAM = 1,  /* acattn_fwd_stream.hip: one wave per 16-row query block, no LDS staging (L <= 208) */
   ACATTN_FWD_STAGED = 2,  /* acattn_fwd_dma.hip / acattn_fwd_fast.hip: K, Ka, V, gate logits staged in LDS (L <= 64) */
-  ACATTN_FWD_GENERAL = 3  /* acattn_fwd.hip: every option, explicit randomness, probability dumps */
+  ACATTN_FWD_GENERAL = 3, /* acattn_fwd.hip: every option, explicit randomness, probability dumps (L <= 208) */
+  ACATTN_FWD_LONG = 4     /* acattn_long_fwd.inc: key tiles in a run-time loop, three sweeps; any L up to
+                             acattn_max_sequence_length(), every option but two_level = 0 and the probability dumps.
+                             The automatic choice for L > 208; any other pinned kernel fails there. */
 };
 int acattn_select_forward_kernel(int which);
 
+/* [added within ABI 34] The largest sequence length L the attention core accepts (496: 31 key tiles of 16). */
+int acattn_max_sequence_length(void);
+
 /* The same for acattn_calibrated_attention_bwd. */
 enum {
-  ACATTN_BWD_AUTO = 0,    /* training configuration: row-resident for L <= 64, streaming (io.workspace given) beyond */
+  ACATTN_BWD_AUTO = 0,    /* training configuration: row-resident for L <= 64, streaming (io.workspace given) up to 208;
+                             L > 208: the long form (io.workspace required) */
   ACATTN_BWD_STREAM = 1,  /* acattn_bwd_stream.hip: row kernel + key kernel, tiles rebuilt from the saved normalisers */
-  ACATTN_BWD_ROW = 2      /* acattn_bwd_fast.hip / acattn_bwd.hip: a query block's whole row in registers */
+  ACATTN_BWD_ROW = 2,     /* acattn_bwd_fast.hip / acattn_bwd.hip: a query block's whole row in registers */
+  ACATTN_BWD_LONG = 3     /* acattn_long_bwd.inc: row kernel + key kernel with run-time tile loops; any L up to
+                             acattn_max_sequence_length(), every option but two_level = 0, the second cotangent set and
+                             dgate_summed; needs io.workspace.  The automatic choice for L > 208; any other pinned kernel
+                             fails there. */
 };
 int acattn_select_backward_kernel(int which);
 
