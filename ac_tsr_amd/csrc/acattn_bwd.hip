@@ -11,7 +11,9 @@ int acattn_launch_bwd_general_dh128(const acattn_problem& p, const acattn_bwd_io
 
 int acattn_launch_bwd_fast(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream);
 int acattn_launch_bwd_stream(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream);
-int acattn_launch_bwd_onerow(const acattn_problem& p, const acattn_bwd_io& io, bool accumulate, hipStream_t stream);
+int acattn_launch_bwd_attack(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream, float* gate_zero = nullptr);  // acattn_bwd_attack.hip
+// `gate_zeroed`: the head-summed gate gradient already holds zeros (the attack-side launch in front wrote them): no fill
+int acattn_launch_bwd_onerow(const acattn_problem& p, const acattn_bwd_io& io, bool accumulate, hipStream_t stream, bool gate_zeroed = false);
 int acattn_launch_bwd_long(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream);  // acattn_long_bwd.hip
 
 namespace {
@@ -27,6 +29,11 @@ int acattn_bwd_kernel_choice(int which) {
 bool acattn_bwd_onerow_applies(const acattn_problem& p, const acattn_bwd_io& io);
 
 namespace {
+// ACATTN_BWD_ATTACK=0 (A/B runs): attack-only launches stay on the row-resident kernel, the one-row launch keeps its fill
+bool attack_kernel_enabled() {
+  static const bool on = getenv("ACATTN_BWD_ATTACK") ? atoi(getenv("ACATTN_BWD_ATTACK")) != 0 : true;
+  return on;
+}
 bool onerow_split_applies(const acattn_problem& p, const acattn_bwd_io& io) {
   static const bool split = getenv("ACATTN_ONEROW_SPLIT") ? atoi(getenv("ACATTN_ONEROW_SPLIT")) != 0 : true;
   if (!(split && (io.d_attack_mask || io.d_penalty_part) && io.read_rows && io.n_read_rows == 1 && !io.active_qblocks && !io.attack_only && p.L <= 64))
@@ -74,7 +81,8 @@ int acattn_launch_bwd(const acattn_problem& p, const acattn_bwd_io& io, hipStrea
     return -1;
   }
   // training hot paths (structured mask, counter RNG, gate, two_level), -100 = not applicable:
-  //   L <= 64: the row-resident kernel (acattn_bwd_fast.hip, one recomputation, a query block's row in registers).
+  //   L <= 64: the row-resident kernel (acattn_bwd_fast.hip, one recomputation, a query block's row in registers);
+  //     an attack-only launch without a context cotangent takes the attack-side kernel (acattn_bwd_attack.hip).
   //     Inside the training step at B = 512, L = 50 its four calls take 71 / 108 / 103 / 57 us against 80 / 112 / 110 /
   //     92 us of the streaming pair (same box, same step: 1.76 against 1.81 ms per step); the attack-only call
   //     (dqa, dka alone) gains most.  In isolation with all three cotangents the order was the other way round
@@ -94,12 +102,17 @@ int acattn_launch_bwd(const acattn_problem& p, const acattn_bwd_io& io, hipStrea
       mask_io.d_ctx_attacked = mask_io.d_ctx_calibrated = nullptr;
       mask_io.n_read_rows = 0;   // no block holds a read position
       mask_io.attack_only = 1;   // dqa, dka alone: everything else is written by the one-row launch
-      const int rc_mask = acattn_launch_bwd_fast(p, mask_io, stream);
+      // the attack-side kernel (acattn_bwd_attack.hip) where it applies; it also writes the zeros of the head-summed gate
+      // gradient the one-row launch adds its read row to
+      float* gate_zero = io.dgate_logits && io.dgate_summed ? io.dgate_logits : nullptr;
+      int rc_mask = attack_kernel_enabled() ? acattn_launch_bwd_attack(p, mask_io, stream, gate_zero) : -100;
+      const bool gate_zeroed = rc_mask == 0 && gate_zero;
+      if (rc_mask == -100) rc_mask = acattn_launch_bwd_fast(p, mask_io, stream);
       if (rc_mask == 0) {
         acattn_bwd_io row_io = io;
         row_io.d_attack_mask = nullptr;
         row_io.d_penalty_part = nullptr;
-        const int rc_row = acattn_launch_bwd_onerow(p, row_io, true, stream);
+        const int rc_row = acattn_launch_bwd_onerow(p, row_io, true, stream, gate_zeroed);
         if (rc_row != -100) return rc_row;
         // the mask launch ran: the read row's chain must not be dropped silently
         acattn_set_error("attention backward: the mask-only launch ran but the one-row kernel does not cover this problem (read-row chain not computed)");
@@ -116,6 +129,10 @@ int acattn_launch_bwd(const acattn_problem& p, const acattn_bwd_io& io, hipStrea
   static const bool short_stream = getenv("ACATTN_BWD_SHORT_STREAM") && atoi(getenv("ACATTN_BWD_SHORT_STREAM")) != 0;
   const bool short_rows = p.L <= 64 && !short_stream;
   if (which == ACATTN_BWD_AUTO && short_rows) {
+    if (io.attack_only && attack_kernel_enabled()) {  // dqa, dka from a mask cotangent alone: acattn_bwd_attack.hip
+      const int rc_attack = acattn_launch_bwd_attack(p, io, stream);
+      if (rc_attack != -100) return rc_attack;
+    }
     const int rc_fast = acattn_launch_bwd_fast(p, io, stream);
     if (rc_fast != -100) return rc_fast;
   }

@@ -1290,9 +1290,9 @@ extern "C" int acattn_debug_onerow_stamps(unsigned long long* host, int n_words)
 
 // Returns -100 when the one-row form does not apply.
 template <int DH>
-int launch_onerow(const acattn_problem& p, const acattn_bwd_io& io, bool accumulate, hipStream_t stream) {
+int launch_onerow(const acattn_problem& p, const acattn_bwd_io& io, bool accumulate, bool gate_zeroed, hipStream_t stream) {
   const dim3 grid(p.B * p.n_heads), block(64);
-  if (io.dgate_logits && io.dgate_summed) {  // the heads add their read row into a zeroed [B,L,L]
+  if (io.dgate_logits && io.dgate_summed && !gate_zeroed) {  // the heads add their read row into a zeroed [B,L,L]
     const int rc = acattn_launch_zero(io.dgate_logits, (size_t)p.B * p.L * p.L, stream);
     if (rc) return rc;
   }
@@ -1359,13 +1359,13 @@ bool acattn_bwd_onerow_applies(const acattn_problem& p, const acattn_bwd_io& io)
          p.adversarial && p.combine_option == ACATTN_COMBINE_GATE && p.two_level && (dh == 16 || dh == 32 || dh == 64 || dh == 128);
 }
 
-int acattn_launch_bwd_onerow(const acattn_problem& p, const acattn_bwd_io& io, bool accumulate, hipStream_t stream) {
+int acattn_launch_bwd_onerow(const acattn_problem& p, const acattn_bwd_io& io, bool accumulate, hipStream_t stream, bool gate_zeroed) {
   if (!acattn_bwd_onerow_applies(p, io)) return -100;
   switch (p.H / p.n_heads) {
-    case 16: return launch_onerow<16>(p, io, accumulate, stream);
-    case 32: return launch_onerow<32>(p, io, accumulate, stream);
-    case 64: return launch_onerow<64>(p, io, accumulate, stream);
-    case 128: return launch_onerow<128>(p, io, accumulate, stream);  // [r3]
+    case 16: return launch_onerow<16>(p, io, accumulate, gate_zeroed, stream);
+    case 32: return launch_onerow<32>(p, io, accumulate, gate_zeroed, stream);
+    case 64: return launch_onerow<64>(p, io, accumulate, gate_zeroed, stream);
+    case 128: return launch_onerow<128>(p, io, accumulate, gate_zeroed, stream);  // [r3]
   }
   return -100;
 }

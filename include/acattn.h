@@ -765,7 +765,11 @@ int acattn_max_sequence_length(void);
 /* The same for acattn_calibrated_attention_bwd. */
 enum {
   ACATTN_BWD_AUTO = 0,    /* training configuration: row-resident for L <= 64, streaming (io.workspace given) up to 208;
-                             L > 208: the long form (io.workspace required) */
+                             L > 208: the long form (io.workspace required).  Only here: the one-row form
+                             (acattn_bwd_stream.hip) and, for L <= 64, acattn_bwd_attack.hip: an attack-only launch whose
+                             only cotangent is the attack mask's (dqa, dka from the soft-max of the mask scores alone;
+                             also the mask launch in front of the one-row form).  ACATTN_BWD_ATTACK=0 in the environment
+                             leaves those launches on the row-resident kernel. */
   ACATTN_BWD_STREAM = 1,  /* acattn_bwd_stream.hip: row kernel + key kernel, tiles rebuilt from the saved normalisers */
   ACATTN_BWD_ROW = 2,     /* acattn_bwd_fast.hip / acattn_bwd.hip: a query block's whole row in registers */
   ACATTN_BWD_LONG = 3     /* acattn_long_bwd.inc: row kernel + key kernel with run-time tile loops; any L up to
