@@ -63,6 +63,8 @@ int check_problem(const acattn_problem* p) {
 
 void acattn_set_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
 
+int acattn_launch_bwd_attack(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream, float* gate_zero);  // acattn_bwd_attack.hip
+
 extern "C" {
 
 int acattn_abi_version(void) { return ACATTN_ABI_VERSION; }
@@ -123,6 +125,18 @@ int acattn_calibrated_attention_bwd(const acattn_problem* p, const acattn_bwd_io
   if (io->part_stride != 0 && io->part_stride < 2 * (p->H / p->n_heads)) return fail("part_stride is smaller than a partial row");
   const int rc = acattn_launch_bwd(*p, *io, (hipStream_t)stream);
   if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
+int acattn_calibrated_attention_bwd_attack_side(const acattn_problem* p, const acattn_bwd_io* io, void* stream) {
+  if (int rc = check_problem(p)) return rc;
+  if (!io) return fail("io is NULL");
+  if (!p->adversarial) return fail("backward is defined for the adversarial (full) operator only");
+  if (!io->attack_mask || !io->row_stats) return fail("backward needs the forward's attack_mask and row_stats");
+  if (!io->dqa || !io->dka) return fail("dqa, dka must be non-NULL");
+  const int rc = acattn_launch_bwd_attack(*p, *io, (hipStream_t)stream, nullptr);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  if (rc == -100) snprintf(g_err, sizeof(g_err), "the attack-side backward (acattn_bwd_attack.hip) does not cover this launch");
   return rc;
 }
 

@@ -82,7 +82,8 @@ int acattn_launch_bwd(const acattn_problem& p, const acattn_bwd_io& io, hipStrea
   }
   // training hot paths (structured mask, counter RNG, gate, two_level), -100 = not applicable:
   //   L <= 64: the row-resident kernel (acattn_bwd_fast.hip, one recomputation, a query block's row in registers);
-  //     an attack-only launch without a context cotangent takes the attack-side kernel (acattn_bwd_attack.hip).
+  //     an attack-only launch without a cotangent of the attacked context takes the attack-side kernel
+  //     (acattn_bwd_attack.hip: the mask cotangent alone, or with d_ctx_calibrated its CTX form).
   //     Inside the training step at B = 512, L = 50 its four calls take 71 / 108 / 103 / 57 us against 80 / 112 / 110 /
   //     92 us of the streaming pair (same box, same step: 1.76 against 1.81 ms per step); the attack-only call
   //     (dqa, dka alone) gains most.  In isolation with all three cotangents the order was the other way round
@@ -129,7 +130,7 @@ int acattn_launch_bwd(const acattn_problem& p, const acattn_bwd_io& io, hipStrea
   static const bool short_stream = getenv("ACATTN_BWD_SHORT_STREAM") && atoi(getenv("ACATTN_BWD_SHORT_STREAM")) != 0;
   const bool short_rows = p.L <= 64 && !short_stream;
   if (which == ACATTN_BWD_AUTO && short_rows) {
-    if (io.attack_only && attack_kernel_enabled()) {  // dqa, dka from a mask cotangent alone: acattn_bwd_attack.hip
+    if (io.attack_only && attack_kernel_enabled()) {  // dqa, dka alone, no d_ctx_attacked: acattn_bwd_attack.hip
       const int rc_attack = acattn_launch_bwd_attack(p, io, stream);
       if (rc_attack != -100) return rc_attack;
     }

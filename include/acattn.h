@@ -766,10 +766,12 @@ int acattn_max_sequence_length(void);
 enum {
   ACATTN_BWD_AUTO = 0,    /* training configuration: row-resident for L <= 64, streaming (io.workspace given) up to 208;
                              L > 208: the long form (io.workspace required).  Only here: the one-row form
-                             (acattn_bwd_stream.hip) and, for L <= 64, acattn_bwd_attack.hip: an attack-only launch whose
-                             only cotangent is the attack mask's (dqa, dka from the soft-max of the mask scores alone;
-                             also the mask launch in front of the one-row form).  ACATTN_BWD_ATTACK=0 in the environment
-                             leaves those launches on the row-resident kernel. */
+                             (acattn_bwd_stream.hip) and, for L <= 64, acattn_bwd_attack.hip: an attack-only launch
+                             without d_ctx_attacked, read rows or a block bitmap.  Its cotangents are the attack mask's
+                             (dqa, dka from the soft-max of the mask scores alone; also the mask launch in front of the
+                             one-row form), d_ctx_calibrated (layer 0 of the attacked-loss walk), or both.
+                             ACATTN_BWD_ATTACK=0 in the environment leaves those launches on the row-resident kernel,
+                             ACATTN_BWD_ATTACK_CTX=0 the ones with d_ctx_calibrated alone. */
   ACATTN_BWD_STREAM = 1,  /* acattn_bwd_stream.hip: row kernel + key kernel, tiles rebuilt from the saved normalisers */
   ACATTN_BWD_ROW = 2,     /* acattn_bwd_fast.hip / acattn_bwd.hip: a query block's whole row in registers */
   ACATTN_BWD_LONG = 3     /* acattn_long_bwd.inc: row kernel + key kernel with run-time tile loops; any L up to
@@ -778,6 +780,12 @@ enum {
                              fails there. */
 };
 int acattn_select_backward_kernel(int which);
+
+/* [added within ABI 34] acattn_calibrated_attention_bwd's arguments, issued on acattn_bwd_attack.hip or not at all: 0 when
+   the attack-side kernel took the launch, -100 when the launch is outside its domain (nothing was launched).  Neither the
+   calling thread's acattn_select_backward_kernel setting nor ACATTN_BWD_ATTACK is consulted; for tests and measurements
+   that must know which kernel ran. */
+int acattn_calibrated_attention_bwd_attack_side(const acattn_problem* p, const acattn_bwd_io* io, void* stream);
 
 #ifdef __cplusplus
 }

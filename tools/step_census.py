@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""step_census.py <kernel_trace.csv> [--sequence]: per-step kernel census from a rocprofv3 --kernel-trace of bench.py
-(--sequence: the launches of one timed step in order, with their durations).
+"""step_census.py <kernel_trace.csv> [--sequence] [--positions <text>]: per-step kernel census from a rocprofv3 --kernel-trace
+of bench.py (--sequence: the launches of one timed step in order, with their durations; --positions <text>: for every position
+in the step whose kernel name holds <text>, min / mean / max of the duration over the timed steps).
 A step is delimited by adam_step_kernel (one launch per step).  bench.py runs the timed (full-schedule, graph) steps and then
 the plain trainer's; the census averages the steps that have the most common kernel count, i.e. the timed ones."""
 import collections
@@ -45,3 +46,17 @@ if want_sequence:
         n = r["Kernel_Name"].replace("void (anonymous namespace)::", "").replace("(anonymous namespace)::", "").replace("void at::native::", "")
         d = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
         print(f"{d:7.1f}  {n.split('(')[0][:72]:72s} {r.get('Grid_Size_X', '')} {r.get('Workgroup_Size_X', '')}")
+if "--positions" in sys.argv[2:]:
+    text = sys.argv[sys.argv.index("--positions") + 1]
+    print()
+    print(f"{steps} steps of {mode} launches; position in the step (0 = the Adam launch that closes the step before), kernel, "
+          "min / mean / max us, range")
+    for pos in range(mode):
+        rs = [rows[a + pos] for a, b in spans]
+        n = rs[0]["Kernel_Name"].replace("void (anonymous namespace)::", "").replace("(anonymous namespace)::", "").split("(")[0]
+        if text not in n:
+            continue
+        d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rs]
+        same = all(r["Kernel_Name"] == rs[0]["Kernel_Name"] for r in rs)
+        print(f"{pos:5d}  {n[:46]:46s} {min(d):6.1f} / {sum(d) / len(d):6.1f} / {max(d):6.1f}   range {max(d) - min(d):5.1f}"
+              + ("" if same else "   (the kernel at this position varies)"))
