@@ -142,6 +142,13 @@ class EmbedProblem(C.Structure):
                 ("keep", _f), ("seed", C.c_uint64), ("seed_device", _f), ("nonzero_out", _f), ("hot_id_plus1", C.c_int64)]
 
 
+class EmbedUserProblem(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("L", C.c_int32), ("H", C.c_int32), ("Di", C.c_int32), ("n_table_rows", C.c_int64),
+                ("n_user_rows", C.c_int64), ("idx", _f), ("user", _f), ("table", _f), ("user_table", _f), ("pos", _f),
+                ("gamma", _f), ("beta", _f), ("eps", C.c_float), ("p_drop", C.c_float), ("keep", _f), ("seed", C.c_uint64),
+                ("seed_device", _f), ("nonzero_out", _f)]
+
+
 EMBED_BWD_CHUNKS = 8
 PENALTY_WS_FLOATS = 1024
 WGRAD_MAX_GROUP = 8
@@ -174,6 +181,10 @@ SYMBOLS = {
     "acattn_dropout_add_layernorm_bwd": (C.c_int, [C.POINTER(LnProblem), _f, _f, _f, _f, _f, C.c_void_p]),
     "acattn_embed_layernorm_fwd": (C.c_int, [C.POINTER(EmbedProblem), _f, _f, C.c_void_p]),
     "acattn_embed_layernorm_bwd": (C.c_int, [C.POINTER(EmbedProblem), _f, _f, C.c_int64, _f, _f, _f, C.c_void_p]),
+    "acattn_embed_user_supported": (C.c_int, [C.c_int32, C.c_int32]),
+    "acattn_embed_user_layernorm_fwd": (C.c_int, [C.POINTER(EmbedUserProblem), _f, _f, C.c_void_p]),
+    "acattn_embed_user_layernorm_bwd": (C.c_int, [C.POINTER(EmbedUserProblem), _f, _f, C.c_int64, C.c_int64, _f, _f, _f, _f, _f,
+                                                  C.c_void_p]),
     "acattn_projections_supported": (C.c_int, [C.c_int32, C.c_int32]),
     "acattn_projections_bwd_workspace_bytes": (C.c_int64, [C.POINTER(ProjProblem)]),
     "acattn_projections_fwd": (C.c_int, [C.POINTER(ProjProblem), C.POINTER(ProjOut), C.c_void_p]),

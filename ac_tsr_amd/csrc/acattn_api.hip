@@ -503,6 +503,45 @@ int acattn_embed_layernorm_bwd(const acattn_embed_problem* p, const float* dy, c
   return rc;
 }
 
+int acattn_embed_user_supported(int32_t H, int32_t Di) {
+  if (H != 64 && H != 128 && H != 256) return 0;
+  return Di > 0 && Di < H && Di % 4 == 0 && (H - Di) % 4 == 0;
+}
+
+static int check_embed_user(const acattn_embed_user_problem* p) {
+  if (!p) return fail("embed_user problem is NULL");
+  if (!acattn_embed_user_supported(p->H, p->Di))
+    return fail("unsupported (H, Di) for the personalised front end: H must be 64, 128 or 256, Di and H - Di positive multiples of 4");
+  if (p->rows < 1 || p->L < 1 || p->rows % p->L != 0) return fail("rows must be a positive multiple of L");
+  if (p->n_table_rows < 1 || p->n_user_rows < 1) return fail("n_table_rows and n_user_rows must be positive");
+  if (!p->idx) return fail("idx must be non-NULL");
+  if (!p->user) return fail("user must be non-NULL");
+  if (!p->table || !p->user_table) return fail("table and user_table must be non-NULL");
+  if (!p->gamma || !p->beta) return fail("gamma and beta must be non-NULL");
+  if (p->p_drop < 0.f || p->p_drop >= 1.f) return fail("p_drop must lie in [0, 1)");
+  return 0;
+}
+
+int acattn_embed_user_layernorm_fwd(const acattn_embed_user_problem* p, float* y, float* stats, void* stream) {
+  if (const int rc = check_embed_user(p)) return rc;
+  if (!y) return fail("y must be non-NULL");
+  if (!stats) return fail("stats must be non-NULL");
+  const int rc = acattn_launch_embed_user_fwd(*p, y, stats, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
+int acattn_embed_user_layernorm_bwd(const acattn_embed_user_problem* p, const float* dy, const float* stats,
+                                    int64_t item_padding_idx, int64_t user_padding_idx, float* d_item, float* d_user,
+                                    float* user_rows_ws, float* d_pos_part, float* dgb_part, void* stream) {
+  if (const int rc = check_embed_user(p)) return rc;
+  if (!dy || !stats) return fail("dy and stats must be non-NULL");
+  const int rc = acattn_launch_embed_user_bwd(*p, dy, stats, item_padding_idx, user_padding_idx, d_item, d_user, user_rows_ws,
+                                              d_pos_part, dgb_part, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
 int acattn_mask_penalty_fwd(const float* m, int64_t n, float* workspace, float* norm, void* stream) {
   if (!m || !workspace || !norm) return fail("m, workspace and norm must be non-NULL");
   if (n < 1) return fail("n must be positive");

@@ -373,6 +373,10 @@ int acattn_launch_linear_wgrad_reduce_many(const float* const* part_w, const flo
 int acattn_launch_embed_fwd(const acattn_embed_problem& p, float* y, float* stats, hipStream_t stream);
 int acattn_launch_embed_bwd(const acattn_embed_problem& p, const float* dy, const float* stats, int64_t padding_idx,
                             float* d_table, float* d_pos_part, float* dgb_part, hipStream_t stream);
+int acattn_launch_embed_user_fwd(const acattn_embed_user_problem& p, float* y, float* stats, hipStream_t stream);
+int acattn_launch_embed_user_bwd(const acattn_embed_user_problem& p, const float* dy, const float* stats,
+                                 int64_t item_padding_idx, int64_t user_padding_idx, float* d_item, float* d_user,
+                                 float* user_rows, float* d_pos_part, float* dgb_part, hipStream_t stream);
 int acattn_launch_penalty_fwd(const float* m, int64_t n, float* ws, float* norm, hipStream_t stream);
 int acattn_launch_penalty_partial(const float* m, int64_t n, float* part, hipStream_t stream);
 // acattn_fwd_out.penalty_part: did the forward launch of this host thread fill it itself? (acattn_fwd_stream.hip)

@@ -321,6 +321,50 @@ int acattn_embed_layernorm_fwd(const acattn_embed_problem* p, float* y, float* s
 int acattn_embed_layernorm_bwd(const acattn_embed_problem* p, const float* dy, const float* stats, int64_t padding_idx,
                                float* d_table, float* d_pos_part, float* dgb_part, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Within ABI 34 (additions only): the personalised front end of ACSSEPT,
+ * y = dropout(LayerNorm(cat(item_embedding[idx], user_embedding[user] over L) + position_embedding[position]))
+ * (recbole/model/sequential_recommender/acssept.py:120-131).  Columns [0, Di) of row r = b*L + l come from
+ * table[idx[r]], columns [Di, H) from user_table[user[b]].  H in {64, 128, 256}; Di and H - Di positive multiples of 4
+ * (a 16-byte lane never straddles the seam). */
+typedef struct acattn_embed_user_problem {
+  int32_t rows, L, H;     /* rows = B*L; row r sits at position r % L of sequence r / L */
+  int32_t Di;             /* item_hidden_size: width of `table`; user_hidden_size = H - Di is the width of `user_table` */
+  int64_t n_table_rows;   /* rows of `table` (ids outside [0, n) are clamped, never dereferenced out of bounds) */
+  int64_t n_user_rows;    /* rows of `user_table` (clamped likewise) */
+  const int64_t* idx;     /* [rows] item ids (item_seq, row-major [B,L]) */
+  const int64_t* user;    /* [rows / L] user ids, one per sequence */
+  const float* table;     /* [n_table_rows,Di] item_embedding.weight */
+  const float* user_table;/* [n_user_rows,H-Di] user_embedding.weight */
+  const float* pos;       /* [>=L,H] position_embedding.weight, or NULL (use_position_embedding: False) */
+  const float* gamma;     /* [H] LayerNorm.weight */
+  const float* beta;      /* [H] LayerNorm.bias */
+  float eps;              /* layer_norm_eps */
+  float p_drop;           /* hidden_dropout_prob in training, 0 in eval (the dropout FOLLOWS the norm) */
+  const uint8_t* keep;    /* optional explicit keep mask [rows,H]; NULL = counter RNG from (seed, seed_device) */
+  uint64_t seed;
+  const uint64_t* seed_device;
+  uint8_t* nonzero_out;   /* optional [rows]: receives idx != 0 (abstract_recommender.py:137); forward only */
+} acattn_embed_user_problem;
+
+/* 1 if the front end above takes hidden size H split at column Di, else 0 (acssept.py:33-35: H = item + user width). */
+int acattn_embed_user_supported(int32_t H, int32_t Di);
+
+/* acssept.py:120-131 in one launch.  stats[rows,2] receives (mean, 1/std) per row for the backward. */
+int acattn_embed_user_layernorm_fwd(const acattn_embed_user_problem* p, float* y, float* stats, void* stream);
+
+/* The backward of acssept.py:120-131.  d_item [n_table_rows,Di] and d_user [n_user_rows,H-Di] (each may be NULL) must be
+ * ZERO-INITIALISED by the caller: rows are accumulated with float atomics; item rows whose id == item_padding_idx and
+ * user rows whose id == user_padding_idx are skipped (nn.Embedding(padding_idx=0): acssept.py:57-59); pass -1 for none.
+ * A user may occur in any number of sequences.  user_rows_ws: [rows,H-Di] floats of scratch, or NULL.  Given, the user
+ * half of every row's gradient is stored there and a second small launch sums each sequence over its L positions before it
+ * touches d_user (one atomic per sequence and column); NULL scatters per row like the item half (L atomics per address).
+ * d_pos_part and dgb_part as in acattn_embed_layernorm_bwd ([ACATTN_EMBED_BWD_CHUNKS, L, H] and
+ * [ACATTN_EMBED_BWD_CHUNKS * L, 2, H], or NULL). */
+int acattn_embed_user_layernorm_bwd(const acattn_embed_user_problem* p, const float* dy, const float* stats,
+                                    int64_t item_padding_idx, int64_t user_padding_idx, float* d_item, float* d_user,
+                                    float* user_rows_ws, float* d_pos_part, float* dgb_part, void* stream);
+
 /* out[bt, c] = sum_r x[bt, r, c]  (x is [batch, R, C] contiguous).  The reductions of the training step's backward:
  * bias gradients (sum over B*L rows), split-K slabs, per-(b,head) parameter partials, per-head gate gradients. */
 int acattn_sum_rows(const float* x, float* out, int32_t batch, int32_t R, int32_t C, void* stream);
