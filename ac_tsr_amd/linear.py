@@ -5,9 +5,9 @@ The forward and the input gradient are ordinary GEMMs (hipBLASLt via torch).  Th
 dW[N,K] = sum_m g[m,n] x[m,k] is a GEMM whose reduction dimension is B*L: on MI355X / ROCm 7.2 hipBLASLt's
 heuristic answers it with a stream-K kernel that takes 110-125 us, rocBLAS takes 25-50 us but is 20x
 slower on the step's one large GEMM (tools/gemm_probe.py, profiles/).  dW and db therefore come from
-acattn_linear_wgrad (csrc/acattn_linear.hip): one pass over x and dy feeding fp32 MFMAs, two launches per layer
-instead of the five of a split-K built from library calls.  Parameters stay ordinary nn.Linear weights
-(state-dict keys are load-bearing, recbole/trainer/trainer.py:672-683).
+acattn_linear_wgrad (csrc/acattn_linear.hip): one pass over x and dy feeding split bf16 (or fp32) MFMAs, two
+launches per layer instead of the five of a split-K built from library calls.  Parameters stay ordinary
+nn.Linear weights (state-dict keys are load-bearing, recbole/trainer/trainer.py:672-683).
 """
 from __future__ import annotations
 

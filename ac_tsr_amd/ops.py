@@ -456,7 +456,8 @@ def sum_rows0(x: torch.Tensor, state=None) -> torch.Tensor:
 
 def linear_wgrad(x2: torch.Tensor, g2: torch.Tensor, want_bias: bool, state=None):
     """(dW [N,K], db [N] or None) of y = x W^T + b from x2 [M,K] and dy g2 [M,N] through acattn_linear_wgrad
-    (one pass over both matrices, fp32 MFMA).  No autograd: used inside backward functions."""
+    (one pass over both matrices; split bf16 MFMAs, or fp32 MFMAs for short and long launches and under
+    acattn_linear_products(0)).  No autograd: used inside backward functions."""
     if state is not None and state.deferring():
         return linear_wgrad_grouped([(x2, g2, want_bias)], state)[0]
     assert x2.is_cuda and x2.dtype == torch.float32 and g2.dtype == torch.float32 and x2.shape[0] == g2.shape[0]

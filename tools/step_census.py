@@ -51,12 +51,16 @@ if "--positions" in sys.argv[2:]:
     print()
     print(f"{steps} steps of {mode} launches; position in the step (0 = the Adam launch that closes the step before), kernel, "
           "min / mean / max us, range")
+    per_step = [0.0] * steps  # the matching launches of each step, summed
     for pos in range(mode):
         rs = [rows[a + pos] for a, b in spans]
         n = rs[0]["Kernel_Name"].replace("void (anonymous namespace)::", "").replace("(anonymous namespace)::", "").split("(")[0]
         if text not in n:
             continue
         d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rs]
+        per_step = [s + v for s, v in zip(per_step, d)]
         same = all(r["Kernel_Name"] == rs[0]["Kernel_Name"] for r in rs)
         print(f"{pos:5d}  {n[:46]:46s} {min(d):6.1f} / {sum(d) / len(d):6.1f} / {max(d):6.1f}   range {max(d) - min(d):5.1f}"
               + ("" if same else "   (the kernel at this position varies)"))
+    print(f"  sum  {'of these launches, per step':46s} {min(per_step):6.1f} / {sum(per_step) / steps:6.1f} / {max(per_step):6.1f}"
+          f"   range {max(per_step) - min(per_step):5.1f}")
