@@ -166,6 +166,9 @@ SYMBOLS = {
     "acattn_calibrated_attention_fwd": (C.c_int, [C.POINTER(Problem), C.POINTER(FwdOut), C.c_void_p]),
     "acattn_calibrated_attention_bwd": (C.c_int, [C.POINTER(Problem), C.POINTER(BwdIO), C.c_void_p]),
     "acattn_calibrated_attention_bwd_attack_side": (C.c_int, [C.POINTER(Problem), C.POINTER(BwdIO), C.c_void_p]),
+    "acattn_unnorm_attention_supported": (C.c_int, [C.POINTER(Problem)]),
+    "acattn_unnorm_attention_fwd": (C.c_int, [C.POINTER(Problem), C.POINTER(FwdOut), C.c_void_p]),
+    "acattn_unnorm_attention_bwd": (C.c_int, [C.POINTER(Problem), C.POINTER(BwdIO), C.c_void_p]),
     "acattn_spatial_attention_bwd": (C.c_int, [C.POINTER(Problem), C.POINTER(SpatialBwdIO), C.c_void_p]),
     "acattn_spatial_attention_bwd_workspace_bytes": (C.c_int64, [C.POINTER(Problem)]),
     "acattn_spatial_affines": (C.c_int, [C.POINTER(Problem), _f, C.c_void_p]),

@@ -65,9 +65,32 @@ void acattn_set_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", ms
 
 int acattn_launch_bwd_attack(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream, float* gate_zero);  // acattn_bwd_attack.hip
 
+// acattn_unnorm.hip: the un-normalised core of ACSSEPT (validation included: they set the error text themselves)
+int acattn_unnorm_supported(const acattn_problem& p);
+int acattn_launch_unnorm_fwd(const acattn_problem& p, const acattn_fwd_out& o, hipStream_t stream);
+int acattn_launch_unnorm_bwd(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream);
+
 extern "C" {
 
 int acattn_abi_version(void) { return ACATTN_ABI_VERSION; }
+
+int acattn_unnorm_attention_supported(const acattn_problem* p) { return p ? acattn_unnorm_supported(*p) : 0; }
+
+int acattn_unnorm_attention_fwd(const acattn_problem* p, const acattn_fwd_out* out, void* stream) {
+  if (!p || !out) return fail("problem and out must be non-NULL");
+  int rc = acattn_launch_unnorm_fwd(*p, *out, (hipStream_t)stream);
+  if (rc == 0 && out->penalty_part)
+    rc = acattn_launch_penalty_rows(out->attack_mask, p->B, p->n_heads, p->L, out->penalty_part, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
+int acattn_unnorm_attention_bwd(const acattn_problem* p, const acattn_bwd_io* io, void* stream) {
+  if (!p || !io) return fail("problem and io must be non-NULL");
+  const int rc = acattn_launch_unnorm_bwd(*p, *io, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
 
 int acattn_max_sequence_length(void) { return ACATTN_MAX_L; }
 

@@ -1,7 +1,7 @@
 """dropout(LayerNorm(cat(item_embedding[item_seq], user_embedding[user_id] over L) + position_embedding)) as one HIP
 launch forward and one (plus a small row sum for the user table) backward (include/acattn.h:
 acattn_embed_user_layernorm_*): the front end of ACSSEPT.forward (recbole/model/sequential_recommender/acssept.py:120-131).
-Only the front end: the ACSSEPT model needs an encoder this package does not have.
+model.ACSSEPT calls it; the encoder behind it is the un-normalised attention core.
 
 The backward adds both table gradients with float atomics into zero-initialised buffers, skipping the `padding_idx` rows
 like nn.Embedding; the item half joins the hand-over of fused_embed (the loss node's published [n_items, Di] gradient is

@@ -141,13 +141,20 @@ class AttackRTransformerLayer(nn.Module):
 
     def __init__(self, n_heads, hidden_size, intermediate_size, hidden_dropout_prob, attn_dropout_prob, hidden_act,
                  layer_norm_eps, combine_option='fixed', use_order=True, use_distance=True, two_level=True,
-                 rich_calibrated_combine='fixed', seq_length=50, adversarial=True):
-        """`adversarial=False` (not a reference argument; after the reference's own): the spatial calibrator alone --
+                 rich_calibrated_combine='fixed', seq_length=50, adversarial=True, renormalise=True):
+        """`renormalise=False` (not a reference argument): the layer of recbole/model/transformer_layers.py:873-1006, which
+        ACSSEPT builds its encoder from -- same parameters and state-dict keys, but the attacked and the combined attention go
+        into the value product without the three soft-maxes of layers.py:919, 921, 925 (ops.AttentionConfig.renormalise).
+        `adversarial=False` (not a reference argument; after the reference's own): the spatial calibrator alone --
         ctx = dropout(softmax((QK^T + e_order + e_distance) / sqrt(dh) + mask)) . V (layers.py:695-740, 677-680), the
         paper's ablation.  The attack transforms and the gate are still created (state-dict keys do not depend on the
         switch) but are never evaluated and receive no gradient."""
         super().__init__()
         self.adversarial = bool(adversarial)
+        self.renormalise = bool(renormalise)
+        if not self.renormalise and not self.adversarial:
+            raise ValueError("renormalise=False is the adversarial layer of transformer_layers.py; adversarial=False has no "
+                             "mixtures to leave un-normalised")
         self.hidden_size = hidden_size
         self.attack_attention = AttackRMultiHeadAttention(
             n_heads, hidden_size, hidden_dropout_prob, attn_dropout_prob, layer_norm_eps,
@@ -170,7 +177,7 @@ class AttackRTransformerLayer(nn.Module):
             self.anneal_step += 1
         return AttentionConfig(n_heads=self.attack_attention.num_attention_heads, combine_option=self.combine_option,
                                two_level=self.two_level, rich_calibrated_combine=self.rich_calibrated_combine,
-                               adversarial=self.adversarial, anneal_rate=rate)
+                               adversarial=self.adversarial, anneal_rate=rate, renormalise=self.renormalise)
 
     def forward(self, hidden_states, attention_mask, return_attention_prob=False, return_all_attention_prob=False,
                 _rnd=None, _need_attacked=True, _attack_upstream=True, _rows=None, _planes=None):
@@ -183,6 +190,9 @@ class AttackRTransformerLayer(nn.Module):
         called without them splits its weights where it uses them."""
         att = self.attack_attention
         cal = att.calibrator_params()
+        if not self.renormalise and (return_attention_prob or return_all_attention_prob):
+            raise ValueError("renormalise=False: the un-normalised attention core has no probability dumps "
+                             "(return_attention_prob / return_all_attention_prob)")
         if not self.adversarial:
             return self._forward_spatial_only(hidden_states, attention_mask, return_attention_prob, return_all_attention_prob,
                                               _rnd, _rows, _planes)
@@ -304,15 +314,18 @@ class AttackRTransformerEncoder(nn.Module):
 
     def __init__(self, n_layers=2, n_heads=2, hidden_size=64, inner_size=256, hidden_dropout_prob=0.5,
                  attn_dropout_prob=0.5, hidden_act='gelu', layer_norm_eps=1e-12, combine_option='fixed', use_order=True,
-                 use_distance=True, two_level=True, rich_calibrated_combine='fixed', seq_length=50, adversarial=True):
-        """`adversarial=False`: every layer runs the spatial calibrator alone (see AttackRTransformerLayer); the attacked
+                 use_distance=True, two_level=True, rich_calibrated_combine='fixed', seq_length=50, adversarial=True,
+                 renormalise=True):
+        """`renormalise=False`: the encoder of recbole/model/transformer_layers.py (see AttackRTransformerLayer).
+        `adversarial=False`: every layer runs the spatial calibrator alone (see AttackRTransformerLayer); the attacked
         slot of every output pair and every entry of `all_attack_masks` are then None."""
         super().__init__()
         self.adversarial = bool(adversarial)
         layer = AttackRTransformerLayer(
             n_heads, hidden_size, inner_size, hidden_dropout_prob, attn_dropout_prob, hidden_act, layer_norm_eps,
             combine_option, use_order=use_order, use_distance=use_distance, two_level=two_level,
-            rich_calibrated_combine=rich_calibrated_combine, seq_length=seq_length, adversarial=adversarial)
+            rich_calibrated_combine=rich_calibrated_combine, seq_length=seq_length, adversarial=adversarial,
+            renormalise=renormalise)
         self.layer = nn.ModuleList([copy.deepcopy(layer) for _ in range(n_layers)])
 
     def forward(self, hidden_states, attention_mask, output_all_encoded_layers=True, return_attention_prob=False,

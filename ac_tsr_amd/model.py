@@ -18,7 +18,7 @@ from torch import nn
 
 from . import layers
 from .layers import AttackRTransformerEncoder
-from . import ce, fused_embed
+from . import ce, fused_embed, fused_embed_user
 from .linear import embedding_lookup, full_sort_scores
 from .ops import StructuredMask, mask_penalty
 from .state import StepState
@@ -264,6 +264,140 @@ class ACSASRec(SequentialRecommender):
         _, calibrated_output, _ = self.forward(item_seq, item_seq_len, _rnds=_rnds)
         scores = torch.matmul(calibrated_output, self.item_embedding.weight.transpose(0, 1))
         return None, scores
+
+
+class ACSSEPT(SequentialRecommender):
+    """recbole/model/sequential_recommender/acssept.py:21-228: SASRec personalised with a user embedding that is concatenated
+    to every position's item embedding (hidden = item_hidden_size + user_hidden_size), over the calibrated encoder of
+    recbole/model/transformer_layers.py -- the one WITHOUT the re-normalising soft-maxes (layers.AttackRTransformerEncoder
+    with renormalise=False; csrc/acattn_unnorm.hip: 'gate', two-level, MAX_ITEM_LIST_LENGTH <= 64).  Same constructor,
+    methods, return values and state-dict keys; `dataset.num(USER_ID)` gives the user count (Counts)."""
+
+    renormalise = False  # (the trainer asks: the one-walk combined backward is not built for this core)
+
+    def __init__(self, config, dataset):
+        super().__init__(config, dataset)
+        self.n_layers = config['n_layers']
+        self.n_heads = config['n_heads']
+        self.user_hidden_size = config['user_hidden_size']
+        self.item_hidden_size = config['item_hidden_size']
+        self.hidden_size = self.user_hidden_size + self.item_hidden_size  # acssept.py:33-35
+        self.inner_size = config['inner_size']
+        self.hidden_dropout_prob = config['hidden_dropout_prob']
+        self.attn_dropout_prob = config['attn_dropout_prob']
+        self.hidden_act = config['hidden_act']
+        self.layer_norm_eps = config['layer_norm_eps']
+        self.initializer_range = config['initializer_range']
+        self.loss_type = config['loss_type']
+        self.combine_option = config['combine_option']
+        self.rich_calibrated_combine = _cfg(config, 'rich_calibrated_combine')
+        self.two_level = _cfg(config, 'two_level')
+        self.use_position_embedding = _cfg(config, 'use_position_embedding')
+        self.use_order = _cfg(config, 'use_order')
+        self.use_distance = _cfg(config, 'use_distance')
+        self.trainable_mask_loss_weight = _cfg(config, 'trainable_mask_loss_weight')
+        self.dp_mask_penalty = 'local'
+        seq_length = _cfg(config, 'gate_seq_length', 50)  # as ACSASRec: the reference pins the gate to L = 50
+        self.n_users = dataset.num(self.USER_ID)  # acssept.py:54
+
+        self.user_embedding = nn.Embedding(self.n_users, self.user_hidden_size, padding_idx=0)       # joins item_seq
+        self.user_test_embedding = nn.Embedding(self.n_users, self.user_hidden_size, padding_idx=0)  # joins the test items
+        self.item_embedding = nn.Embedding(self.n_items, self.item_hidden_size, padding_idx=0)
+        if self.use_position_embedding:
+            self.position_embedding = nn.Embedding(self.max_seq_length, self.hidden_size)
+        self.trm_encoder = AttackRTransformerEncoder(
+            n_layers=self.n_layers, n_heads=self.n_heads, hidden_size=self.hidden_size, inner_size=self.inner_size,
+            hidden_dropout_prob=self.hidden_dropout_prob, attn_dropout_prob=self.attn_dropout_prob,
+            hidden_act=self.hidden_act, layer_norm_eps=self.layer_norm_eps, combine_option=self.combine_option,
+            use_order=self.use_order, use_distance=self.use_distance, two_level=self.two_level,
+            rich_calibrated_combine=self.rich_calibrated_combine, seq_length=seq_length, renormalise=False)
+        self.LayerNorm = nn.LayerNorm(self.hidden_size, eps=self.layer_norm_eps)
+        self.dropout = nn.Dropout(self.hidden_dropout_prob)
+        if self.trainable_mask_loss_weight:
+            self.mask_loss_weight = nn.Parameter(torch.FloatTensor([0.3]), requires_grad=True)
+        else:
+            self.mask_loss_weight = config['mask_loss_weight']
+        if self.loss_type == 'BPR':
+            self.loss_fct = _BPRLoss()
+        elif self.loss_type == 'CE':
+            self.loss_fct = nn.CrossEntropyLoss()
+        else:
+            raise NotImplementedError("Make sure 'loss_type' in ['BPR', 'CE']!")
+        self.apply(self._init_weights)
+        self.step_state = StepState().attach(self)
+
+    _init_weights = ACSASRec._init_weights
+
+    def forward(self, item_seq, item_seq_len, user_id, _rnds=None, _keep_emb=None, _last_row=None):
+        """acssept.py:120-140 -> (attacked [B,H], calibrated [B,H], attack masks).  The front end is one launch
+        (fused_embed_user), the attention core of every layer the un-normalised pair."""
+        pos = self.position_embedding if self.use_position_embedding else None
+        input_emb, nonzero = fused_embed_user.embed_user_layer_norm(
+            item_seq, user_id, self.item_embedding, self.user_embedding, pos, self.LayerNorm, self.dropout.p, self.training,
+            _keep_emb, return_nonzero=True)
+        mask = StructuredMask(key_valid=nonzero, causal=True)
+        if not self.step_state.prune_dead_work:  # the reference's full schedule (acssept.py:135-139)
+            trm_output = self.trm_encoder(input_emb, mask, output_all_encoded_layers=True, _rnds=_rnds)
+            attacked_output, calibrated_output = trm_output[0][-1]
+            return (self.gather_indexes(attacked_output, item_seq_len - 1),
+                    self.gather_indexes(calibrated_output, item_seq_len - 1), trm_output[1])
+        last = (item_seq_len - 1).view(-1, 1) if _last_row is None else _last_row.view(-1, 1)
+        trm_output = self.trm_encoder(input_emb, mask, output_all_encoded_layers=False, _rnds=_rnds, _last_rows=last)
+        attacked_output, calibrated_output = trm_output[0][-1]
+        return attacked_output.squeeze(1), calibrated_output.squeeze(1), trm_output[1]
+
+    def _cal_loss(self, seq_output, interaction, attack_loss=False):
+        user_id = interaction[self.USER_ID]
+        pos_items = interaction[self.POS_ITEM_ID]
+        if self.loss_type == 'BPR':  # acssept.py:148-161
+            neg_items = interaction[self.NEG_ITEM_ID]
+            user_emb = self.user_embedding(user_id)
+            pos_items_emb = torch.cat([self.item_embedding(pos_items), user_emb], dim=-1)
+            neg_items_emb = torch.cat([self.item_embedding(neg_items), user_emb], dim=-1)
+            pos_score = torch.sum(seq_output * pos_items_emb, dim=-1)
+            neg_score = torch.sum(seq_output * neg_items_emb, dim=-1)
+            return self.loss_fct(pos_score, neg_score)
+        # 'CE' (acssept.py:162-173): logits[b, n] = out[b, :Di] . E[n] + out[b, Di:] . U[user_b].  The second term does not
+        # depend on n: it shifts a row's logits together and cancels in the cross-entropy and in every gradient of it.  What
+        # is left is the full-catalogue cross-entropy of the item half against the [n_items, Di] table.
+        item_half = seq_output[:, :self.item_hidden_size].contiguous()
+        if item_half.is_cuda and ce.supported(self.item_hidden_size) and torch.is_grad_enabled():
+            return ce.full_sort_cross_entropy(item_half, self.item_embedding.weight, pos_items, table_grad=not attack_loss,
+                                              state=self.step_state)
+        return self.loss_fct(full_sort_scores(item_half, self.item_embedding.weight, self.step_state), pos_items)
+
+    def calculate_loss(self, interaction, _rnds=None, _keep_emb=None):
+        """acssept.py:175-191 -> (final_attacked_loss, calibrated_loss)."""
+        last_row = interaction.get("_acattn_last_row") if isinstance(interaction, dict) else None
+        attacked_output, calibrated_output, all_attack_masks = self.forward(
+            interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN], interaction[self.USER_ID], _rnds=_rnds,
+            _keep_emb=_keep_emb, _last_row=last_row)
+        attacked_loss = -self._cal_loss(attacked_output, interaction, attack_loss=True)
+        calibrated_loss = self._cal_loss(calibrated_output, interaction)
+        mask_penalty = torch.mean(torch.stack([_penalty(m) for m in all_attack_masks], dim=0))
+        weight = self.mask_loss_weight[0] if self.trainable_mask_loss_weight else self.mask_loss_weight
+        return attacked_loss + mask_penalty * weight, calibrated_loss
+
+    def _user_test_term(self, output, user_id):
+        """out[:, Di:] . user_test_embedding[user]: the user half of a test item's concatenated embedding (acssept.py:198-203,
+        213-220), the same for every item."""
+        return (output[:, self.item_hidden_size:] * self.user_test_embedding(user_id)).sum(dim=-1)
+
+    def predict(self, interaction):
+        user_id = interaction[self.USER_ID]
+        attacked_output, calibrated_output, _ = self.forward(interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN], user_id)
+        test_item_emb = self.item_embedding(interaction[self.ITEM_ID])
+        Di = self.item_hidden_size
+        score = lambda out: (out[:, :Di] * test_item_emb).sum(dim=-1) + self._user_test_term(out, user_id)
+        return score(attacked_output), score(calibrated_output)
+
+    def full_sort_predict(self, interaction, _rnds=None):
+        user_id = interaction[self.USER_ID]
+        attacked_output, calibrated_output, _ = self.forward(interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN], user_id,
+                                                             _rnds=_rnds)
+        table, Di = self.item_embedding.weight, self.item_hidden_size
+        score = lambda out: torch.matmul(out[:, :Di], table.transpose(0, 1)) + self._user_test_term(out, user_id).unsqueeze(1)
+        return score(attacked_output), score(calibrated_output)
 
 
 class AcBERT4Rec(SequentialRecommender):
@@ -513,3 +647,14 @@ class ItemCount:
 
     def num(self, field):
         return self.n_items
+
+
+class Counts:
+    """`dataset` for ACSSEPT's constructor: `.num(field)` answers the user count for the user-id field and the item count
+    for everything else (acssept.py:54: n_users = dataset.num(USER_ID))."""
+
+    def __init__(self, n_items, n_users, user_field='user_id'):
+        self.n_items, self.n_users, self.user_field = n_items, n_users, user_field
+
+    def num(self, field):
+        return self.n_users if field == self.user_field else self.n_items

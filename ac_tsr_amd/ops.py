@@ -47,6 +47,9 @@ class AttentionConfig:
     rich_calibrated_combine: str = "fixed"  # layers.py:929-936 (only read when two_level is False)
     adversarial: bool = True  # False = spatial calibrator only (BASELINE config 2)
     anneal_rate: float = 1.0
+    # False = ACSSEPT's encoder (recbole/model/transformer_layers.py:920-928): the attacked and the combined mixture go into
+    # the value product as they are, without the soft-maxes of layers.py:919, 921, 925 (_UnnormalisedAttention)
+    renormalise: bool = True
 
 
 @dataclass
@@ -352,6 +355,77 @@ class _CalibratedAttention(torch.autograd.Function):
                 None, None, None, None, None)
 
 
+UNNORM_MAX_L = 64  # csrc/acattn_unnorm.hip holds a query block's row of four key tiles
+
+
+def _check_unnormalised(q, k, v, qa, ka, gate_logits, mask, cfg: AttentionConfig, w_order, w_dist, want_probs: bool):
+    """ValueError naming the limit for everything the un-normalised pair does not take (include/acattn.h:
+    acattn_unnorm_attention_supported); there is no other kernel to fall back to."""
+    what = "attention without re-normalisation (AttentionConfig.renormalise=False)"
+    if not cfg.adversarial:
+        raise ValueError(f"{what} needs the adversarial calibrator (adversarial=True)")
+    if cfg.combine_option != "gate":
+        raise ValueError(f"{what} is built for combine_option 'gate' only, not {cfg.combine_option!r}")
+    if not cfg.two_level:
+        raise ValueError(f"{what} is built for two_level=True only (the one-level form is not)")
+    if want_probs:
+        raise ValueError(f"{what} has no probability dumps (want_probs / return_attention_prob)")
+    if not isinstance(mask, StructuredMask):
+        raise ValueError(f"{what} takes a StructuredMask only; dense masks are not built")
+    if w_order is None or w_dist is None:
+        raise ValueError(f"{what} needs both spatial terms (order and distance)")
+    for name, t in (("q", q), ("k", k), ("v", v), ("qa", qa), ("ka", ka), ("gate_logits", gate_logits),
+                    ("key_valid", mask.key_valid)):
+        if t is None or not t.is_cuda:
+            raise ValueError(f"{what}: {name} must be a tensor on the GPU (HIP kernels only, no CPU path)")
+    if q.shape[1] > UNNORM_MAX_L:
+        raise ValueError(f"{what} is built for sequence length L <= {UNNORM_MAX_L}, got {q.shape[1]}")
+    if q.shape[2] % cfg.n_heads or q.shape[2] // cfg.n_heads not in (16, 32, 64):
+        raise ValueError(f"{what} is built for head sizes 16, 32 and 64, got hidden {q.shape[2]} / {cfg.n_heads} heads")
+
+
+class _UnnormalisedAttention(torch.autograd.Function):
+    """ACSSEPT's attention core (csrc/acattn_unnorm.hip) on the attn_launch path.  The first 11 inputs can carry gradients.
+    Outputs (ctx_attacked, ctx_calibrated, M, penalty rows or None)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar, mask, cfg: AttentionConfig,
+                p_drop: float, rnd, seed: int, seed_tensor=None, read_rows=None, attack_upstream=True, state=_DEFAULT_STATE,
+                gate_is_prob=False):
+        lib = _lib.load()
+        ctx.set_materialize_grads(False)
+        keep = []
+        prob = _fill_problem(q, k, v, qa, ka, gate_logits, mask, w_order.reshape(-1), b_order, w_dist.reshape(-1), b_dist,
+                             scalar, None, cfg, p_drop, rnd, seed, keep, seed_tensor, gate_is_prob)
+        if not attn_launch.unnorm_attention_supported(lib, prob):
+            raise ValueError("attention without re-normalisation: configuration outside acattn_unnorm_attention_supported")
+        want_pen = bool(PENALTY_ROWS and any(ctx.needs_input_grad[:11]))
+        ctx_att, ctx_cal, M, stats, pen = attn_launch.unnorm_attention_fwd_launch(lib, prob, q, cfg.n_heads,
+                                                                                 want_penalty=want_pen)
+        ctx.cfg, ctx.p_drop, ctx.rnd, ctx.seed, ctx.mask, ctx.seed_tensor = cfg, p_drop, rnd, seed, mask, seed_tensor
+        ctx.gate_is_prob, ctx.attack_upstream, ctx.state = gate_is_prob, attack_upstream, state
+        ctx.read_rows = read_rows.contiguous() if read_rows is not None and read_rows.shape[1] <= 4 else None
+        ctx.save_for_backward(q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar, M, stats)
+        return ctx_att, ctx_cal, M, pen
+
+    @staticmethod
+    def backward(ctx, d_att, d_cal, d_M, d_pen):
+        # Never mutates saved state: the trainer walks this node twice (retain_graph=True, recbole/trainer/trainer.py:677,684).
+        (q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar, M, stats) = ctx.saved_tensors
+        cfg = ctx.cfg
+        lib = _lib.load()
+        keep = []
+        d_att, d_cal, d_M, d_pen = (None if t is None else t.contiguous() for t in (d_att, d_cal, d_M, d_pen))
+        attack_only = ctx.state.attack_pass_only and not ctx.attack_upstream
+        prob = _fill_problem(q, k, v, qa, ka, gate_logits, ctx.mask, w_order.reshape(-1), b_order, w_dist.reshape(-1), b_dist,
+                             scalar, None, cfg, ctx.p_drop, ctx.rnd, ctx.seed, keep, ctx.seed_tensor, ctx.gate_is_prob)
+        res = attn_launch.unnorm_attention_bwd_launch(lib, prob, q, cfg.n_heads, M, stats, d_att=d_att, d_cal=d_cal, d_M=d_M,
+                                                      d_pen=d_pen, read_rows=ctx.read_rows, attack_only=attack_only)
+        grads = _CalibratedAttention._finish_backward(lib, attack_only, *res, q.shape[2] // cfg.n_heads, w_order, b_order, w_dist,
+                                                      b_dist, scalar, None, ctx.state)
+        return tuple(grads[:11]) + (None,) * 10
+
+
 def calibrated_attention(q, k, v, qa, ka, gate_logits, mask, cfg: AttentionConfig, *, w_order=None, b_order=None,
                          w_dist=None, b_dist=None, scalar=None, rich_ratio=None, p_drop: float = 0.0,
                          rnd: Optional[ExplicitRandomness] = None, seed: Optional[int] = None,
@@ -378,6 +452,15 @@ def calibrated_attention(q, k, v, qa, ka, gate_logits, mask, cfg: AttentionConfi
     """
     if rnd is None and seed is None:
         seed = state.draw_seed()  # one 63-bit seed per call, salted per data-parallel rank
+    if not cfg.renormalise:
+        # ACSSEPT's core: a kernel pair of its own, never the normalised kernels (a limit it does not cover is an error)
+        _check_unnormalised(q, k, v, qa, ka, gate_logits, mask, cfg, w_order, w_dist, want_probs)
+        ctx_att, ctx_cal, M, pen = _UnnormalisedAttention.apply(
+            q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar, mask, cfg, p_drop, rnd, seed or 0,
+            seed_tensor, read_rows, attack_upstream, state, gate_is_prob)
+        if pen is not None:
+            M._acattn_pen = pen  # see PENALTY_ROWS
+        return ctx_att, ctx_cal, M, {}
     # seed_tensor (device int64[1]) is added to `seed` inside the kernels: under hipGraph capture `seed` is frozen
     # into the graph, the tensor is what changes between replays (trainer.enable_graph)
     outs = _CalibratedAttention.apply(q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar,

@@ -42,6 +42,9 @@ class AttackSASRecTrainer:
             raise ValueError("combined_backward=True shares one walk between the attacked and the calibrated loss; a model "
                              "with adversarial_calibrator=False has no attacked loss: use the default two-pass step "
                              "(its second pass is then empty)")
+        if self.combined_backward and not getattr(model, 'renormalise', True):
+            raise ValueError("combined_backward=True is not built for a model on the un-normalised attention core (ACSSEPT: "
+                             "its autograd node has no backward_pair); use the default two-pass step")
         if self.combined_backward:
             from .combined import instrument_package
             instrument_package()  # before any forward whose graph will be walked
@@ -229,6 +232,9 @@ class AttackSASRecTrainer:
         rest after.  `debug_dump`: path of a .dot file that receives the captured graph (hipGraphDebugDotPrint)."""
         assert self.device.type == 'cuda'
         assert warmup >= 1, "at least one eager step must precede the capture (it creates the optimizer's state)"
+        if not getattr(self.model, 'renormalise', True):
+            raise ValueError("a model on the un-normalised attention core (ACSSEPT) trains eagerly only: capturing its step "
+                             "into a hipGraph is not supported yet (DESIGN.md section 4.11)")
         for m in self.model.modules():
             # 'annealing' advances a host-side step counter on every forward (recbole/model/layers.py:890-891) and the
             # rate travels to the kernel by value: a replayed graph would keep the rate of the capture forever

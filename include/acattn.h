@@ -831,6 +831,42 @@ int acattn_select_backward_kernel(int which);
    that must know which kernel ran. */
 int acattn_calibrated_attention_bwd_attack_side(const acattn_problem* p, const acattn_bwd_io* io, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * [added within ABI 34: new entry points only, the structs are unchanged] The UN-NORMALISED attention core of ACSSEPT
+ * (acssept.py:17 builds its encoder from recbole/model/transformer_layers.py:873-1006, not from recbole/model/layers.py).  That
+ * encoder shares every parameter and state-dict key with the one above, but transformer_layers.py:920-928 has none of the
+ * three softmax(. + attention_mask) re-normalisations of layers.py:919, 921, 925: per head, with P = after_spatial
+ * (transformer_layers.py:823-867), M the attack mask (:785-802), N ~ randn and g = sigmoid(gate(query)) (:901),
+ *     A_att = P M + N (1 - M)                      transformer_layers.py:921-922
+ *     A_w   = g P + (1 - g) P exp(1 - M)           transformer_layers.py:924, :901-902
+ *     ctx_attacked = A_att . V,  ctx_calibrated = A_w . V      transformer_layers.py:805
+ * A kernel pair of its own (csrc/acattn_unnorm.hip); never a fallback to or from acattn_calibrated_attention_*.
+ *
+ * Supported (acattn_unnorm_attention_supported answers 1 / 0 from the configuration alone, without a launch): adversarial = 1,
+ * combine_option GATE, two_level = 1, mask_mode STRUCTURED (causal or not), 1 <= L <= 64, head size 16, 32 or 64, rng_mode
+ * EXPLICIT (noise, keep_after, keep_mask; p_drop = 0 = no dropout, keep_before is not read) or COUNTER (seed, seed_device; the
+ * draws of acattn_rng_materialize), gate_is_prob 0 or 1; both spatial terms must be present; `affine` is ignored.  Anything
+ * else: -1 and a text that names the limit.
+ *
+ * Consequences of the missing re-normalisation, all as in the reference: where M = 0 (padded keys, future keys under the
+ * causal mask) A_att = N, so ctx_attacked sums over ALL L keys -- V of padded and future positions included: a NaN or Inf
+ * there reaches ctx_attacked.  A query row without an allowed key (left padding under the causal mask) gets the soft-max
+ * over all L keys, the mask's common -10000 dropped; the reference's fp32 rounding of `score - 10000` is NOT reproduced
+ * (its float64 value is).  ctx_attacked is O(sqrt(L) |V|).
+ *
+ * Forward: writes ctx_attacked, ctx_calibrated, attack_mask (all required), row_stats when given and penalty_part when
+ * given (acattn_mask_penalty_rows behind the launch).  row_stats [B,nh,L,ACATTN_NSTAT]: slot 0 = the log-normaliser of P's
+ * row, slot 1 = that of M's row, both in LOG2 units of the scaled, masked scores (P before dropout = exp2(log2(e) x - slot 0));
+ * slots 2..7 are written as zeros.  A non-NULL probability dump (after_spatial ...) is an error.
+ * Backward: rebuilds P and M (before dropout) from q, k, qa, ka, the calibrator parameters and row_stats, replays the keep
+ * bits and the noise; every combination of d_ctx_attacked, d_ctx_calibrated, d_attack_mask, d_penalty_part (NULL = zero);
+ * writes dq, dk, dv, dqa, dka, dgate_logits ([B,nh,L,L] per-head partials) and the three parameter partials (part_stride
+ * honoured) in full.  active_qblocks, read_rows and attack_only are ignored (every output is written); workspace is unused;
+ * dgate_summed and the second cotangent set (dqa2 ...) are errors.  No float atomics: two launches give the same bits. */
+int acattn_unnorm_attention_supported(const acattn_problem* p);
+int acattn_unnorm_attention_fwd(const acattn_problem* p, const acattn_fwd_out* out, void* stream);
+int acattn_unnorm_attention_bwd(const acattn_problem* p, const acattn_bwd_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,12 @@ sum-first figure covers both of its launches.  The backward accumulates into its
 The yardstick: the new kernel writes the same bytes, reads fewer table bytes and adds one index stream, so it should take no more
 than 1.25 x the item-only kernel each way.  The verdict is printed, nothing is tuned to it.
 
-Usage:  python tools/bench_ssept.py [--out profiles/ssept_front_end.txt]
+`--core`: the un-normalised attention core of ACSSEPT (acattn_unnorm_attention_fwd / _bwd) beside the normalised core's
+row-resident kernels (acattn_calibrated_attention_fwd pinned to ACATTN_FWD_STAGED, _bwd to ACATTN_BWD_ROW) in the same process,
+at B = 512, L = 50, H = 128, 2 heads (head size 64), counter RNG, p_drop 0.5: forward, backward with all three cotangents,
+and the attack-only backward (d_ctx_calibrated + d_penalty_part, attack_only = 1).  Same sampling as above.  No bar is set.
+
+Usage:  python tools/bench_ssept.py [--core] [--out profiles/ssept_front_end.txt | profiles/ssept_core.txt]
 """
 import argparse
 import ctypes as C
@@ -27,14 +32,110 @@ from ac_tsr_amd import _lib  # noqa: E402
 from ac_tsr_amd.ops import _ptr, _stream  # noqa: E402
 
 
+def sample(kernels, a):
+    """{name: [us per launch, ...]}: `a.rounds` device-event samples of `a.inner` launches each, the kernels alternating."""
+    for _ in range(a.warmup):
+        for fn in kernels.values():
+            fn()
+    torch.cuda.synchronize()
+    samples = {k: [] for k in kernels}
+    for _ in range(a.rounds):
+        for k, fn in kernels.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.inner):
+                fn()
+            e1.record()
+            e1.synchronize()
+            samples[k].append(e0.elapsed_time(e1) * 1e3 / a.inner)
+    return samples
+
+
+def core(a):
+    from ac_tsr_amd import attn_launch
+    dev, lib = "cuda", _lib.load()
+    B, L, H, nh, p_drop = 512, 50, 128, 2, 0.5
+    dh, nqb = H // nh, (L + 15) // 16
+    g = torch.Generator().manual_seed(0)
+    f = lambda *s: torch.randn(*s, generator=g).to(dev)
+    q, k, v, qa, ka, gl = f(B, L, H), f(B, L, H), f(B, L, H), f(B, L, H), f(B, L, H), f(B, L, L)
+    scale = 0.3 * (32 / dh) ** 0.5
+    w_order, b_order, w_dist, b_dist, scalar = scale * f(2 * dh), scale * f(1), scale * f(2 * dh), scale * f(1), scale * f(1)
+    lens = torch.randint(1, L + 1, (B,), generator=g)
+    kv = (torch.arange(L)[None, :] < lens[:, None]).to(torch.uint8).to(dev)
+    prob = attn_launch.fill_problem(q, k, v, qa, ka, gl, w_order, b_order, w_dist, b_dist, scalar, nh, p_drop, 1234, None,
+                                    key_valid=kv, causal=True)
+    e = lambda *s: torch.empty(*s, device=dev)
+    outs = {}
+    for name in ("unnorm", "norm"):
+        o = _lib.FwdOut()
+        t = dict(ctx_a=e(B, L, H), ctx_c=e(B, L, H), M=e(B, nh, L, L), stats=e(B, nh, L, _lib.NSTAT))
+        o.ctx_attacked, o.ctx_calibrated, o.attack_mask, o.row_stats = _ptr(t["ctx_a"]), _ptr(t["ctx_c"]), _ptr(t["M"]), _ptr(t["stats"])
+        outs[name] = (o, t)
+    d_att, d_cal, d_M, d_pen = f(B, L, H), f(B, L, H), 1e-3 * f(B, nh, L, L), 1e-3 * f(B, nh, nqb)
+    ws = attn_launch.workspace(lib.acattn_calibrated_attention_bwd_workspace_bytes(C.byref(prob)), dev)
+    ios = {}
+    for name in ("unnorm", "norm"):
+        for pattern in ("all", "attack"):
+            io = _lib.BwdIO()
+            t = dict(g=[e(B, L, H) for _ in range(5)], gate=e(B, nh, L, L), part=e(B * nh, 4 * dh + 4))
+            io.attack_mask, io.row_stats = _ptr(outs[name][1]["M"]), _ptr(outs[name][1]["stats"])
+            if pattern == "all":
+                io.d_ctx_attacked, io.d_ctx_calibrated, io.d_attack_mask = _ptr(d_att), _ptr(d_cal), _ptr(d_M)
+            else:
+                io.d_ctx_calibrated, io.d_penalty_part, io.attack_only = _ptr(d_cal), _ptr(d_pen), 1
+            io.dq, io.dk, io.dv, io.dqa, io.dka = (_ptr(x) for x in t["g"])
+            io.dgate_logits = _ptr(t["gate"])
+            base = t["part"].data_ptr()
+            io.dw_order_part, io.dw_dist_part, io.dsmall_part, io.part_stride = base, base + 8 * dh, base + 16 * dh, 4 * dh + 4
+            if name == "norm":
+                io.workspace = _ptr(ws)
+            ios[name, pattern] = (io, t)
+    lib.acattn_select_forward_kernel(_lib.FWD_STAGED)
+    lib.acattn_select_backward_kernel(_lib.BWD_ROW)
+    chk = lambda rc: _lib.check(rc, "core")
+    kernels = {
+        "unnorm fwd": lambda: chk(lib.acattn_unnorm_attention_fwd(C.byref(prob), C.byref(outs["unnorm"][0]), _stream())),
+        "norm   fwd": lambda: chk(lib.acattn_calibrated_attention_fwd(C.byref(prob), C.byref(outs["norm"][0]), _stream())),
+        "unnorm bwd all": lambda: chk(lib.acattn_unnorm_attention_bwd(C.byref(prob), C.byref(ios["unnorm", "all"][0]), _stream())),
+        "norm   bwd all": lambda: chk(lib.acattn_calibrated_attention_bwd(C.byref(prob), C.byref(ios["norm", "all"][0]), _stream())),
+        "unnorm bwd attack": lambda: chk(lib.acattn_unnorm_attention_bwd(C.byref(prob), C.byref(ios["unnorm", "attack"][0]), _stream())),
+        "norm   bwd attack": lambda: chk(lib.acattn_calibrated_attention_bwd(C.byref(prob), C.byref(ios["norm", "attack"][0]), _stream())),
+    }
+    samples = sample(kernels, a)
+    lib.acattn_select_forward_kernel(_lib.FWD_AUTO)
+    lib.acattn_select_backward_kernel(_lib.BWD_AUTO)
+    assert all(torch.isfinite(t).all() for t in outs["unnorm"][1].values())
+    assert all(torch.isfinite(t).all() for t in ios["unnorm", "all"][1]["g"])
+    qt = lambda v, f_: sorted(v)[min(len(v) - 1, int(f_ * len(v)))]
+    lines = [f"un-normalised attention core (acattn_unnorm.hip) vs the normalised row-resident kernels, B={B} L={L} H={H} heads={nh} "
+             f"(head size {dh}), counter RNG, p_drop={p_drop}",
+             f"device: {torch.cuda.get_device_name(0)}; {a.rounds} rounds x {a.inner} launches per sample, kernels alternating; us per launch",
+             "norm fwd: ACATTN_FWD_STAGED; norm bwd: ACATTN_BWD_ROW; `attack`: d_ctx_calibrated + d_penalty_part, attack_only = 1",
+             f"{'kernel':<18} {'median':>8} {'p10':>8} {'p90':>8}"]
+    for name, vals in samples.items():
+        lines.append(f"{name:<18} {qt(vals, 0.5):8.2f} {qt(vals, 0.1):8.2f} {qt(vals, 0.9):8.2f}")
+    for way in ("fwd", "bwd all", "bwd attack"):
+        r = qt(samples[f"unnorm {way}"], 0.5) / qt(samples[f"norm   {way}"], 0.5)
+        lines.append(f"{way}: unnorm / norm = {r:.3f}")
+    text = "\n".join(lines)
+    print(text, flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        open(a.out, "w").write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--core", action="store_true", help="time the un-normalised attention core beside the normalised one")
     ap.add_argument("--rounds", type=int, default=200)
     ap.add_argument("--inner", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "bench_ssept.py measures on the GPU; there is no CPU path"
+    if a.core:
+        return core(a)
     dev = "cuda"
     lib = _lib.load()
     B, L, Di, Du, N, U, p_drop = 512, 50, 64, 64, 12102, 20000, 0.5
