@@ -5,16 +5,16 @@ their ctypes binding, and host-side mirrors of the reference's operator surface
 (`AttackRTransformerEncoder`, `ACSASRec`, the two-pass trainer step, batch data-parallelism).
 """
 from . import _lib  # noqa: F401
-from .layers import (AttackRMultiHeadAttention, AttackRTransformerEncoder, AttackRTransformerLayer,  # noqa: F401
-                     FeedForward)
-from .model import ACSASRec, ACSSEPT, AcBERT4Rec, Counts, DictConfig, ItemCount, SequentialRecommender  # noqa: F401
-from .ops import (AttentionConfig, ExplicitRandomness, StructuredMask, calibrated_attention,  # noqa: F401
-                  materialize_randomness)
+from .layers import (ACTimeAwareTransformerEncoder, ACTimeAwareTransformerLayer, AttackRMultiHeadAttention,  # noqa: F401
+                     AttackRTransformerEncoder, AttackRTransformerLayer, FeedForward)
+from .model import ACSASRec, ACSSEPT, ACTiSASRec, AcBERT4Rec, Counts, DictConfig, ItemCount, SequentialRecommender  # noqa: F401
+from .ops import (AttentionConfig, ExplicitRandomness, StructuredMask, TimeIntervals, calibrated_attention,  # noqa: F401
+                  materialize_randomness, materialize_time_randomness, timeaware_attention)
 from .trainer import AttackSASRecTrainer, ACSASRecTrainer, is_attack_param  # noqa: F401
 
 __all__ = [
-    "ACSASRec", "ACSSEPT", "AcBERT4Rec", "Counts", "ACSASRecTrainer", "AttackRMultiHeadAttention", "AttackRTransformerEncoder",
+    "ACSASRec", "ACSSEPT", "ACTiSASRec", "ACTimeAwareTransformerEncoder", "ACTimeAwareTransformerLayer", "AcBERT4Rec", "Counts", "ACSASRecTrainer", "AttackRMultiHeadAttention", "AttackRTransformerEncoder",
     "AttackRTransformerLayer", "AttackSASRecTrainer", "AttentionConfig", "DictConfig", "ExplicitRandomness",
     "FeedForward", "ItemCount", "SequentialRecommender", "StructuredMask", "calibrated_attention",
-    "is_attack_param", "materialize_randomness",
+    "is_attack_param", "materialize_randomness", "TimeIntervals", "materialize_time_randomness", "timeaware_attention",
 ]

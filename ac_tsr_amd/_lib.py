@@ -61,6 +61,16 @@ class BwdIO(C.Structure):
     ]
 
 
+class TimeExt(C.Structure):
+    _fields_ = [("pos_k", _f), ("pos_v", _f), ("time_index", _f), ("time_k", _f), ("time_v", _f), ("time_span", C.c_int32),
+                ("p_time", C.c_float), ("keep_time_k", _f), ("keep_time_v", _f), ("time_seed", C.c_uint64),
+                ("time_seed_device", _f)]
+
+
+class TimeGrads(C.Structure):
+    _fields_ = [("d_pos_k", _f), ("d_time_k", _f), ("d_time_v", _f), ("workspace", _f)]
+
+
 class SpatialBwdIO(C.Structure):
     _fields_ = [
         ("d_ctx", _f), ("dq", _f), ("dk", _f), ("dv", _f),
@@ -169,6 +179,11 @@ SYMBOLS = {
     "acattn_unnorm_attention_supported": (C.c_int, [C.POINTER(Problem)]),
     "acattn_unnorm_attention_fwd": (C.c_int, [C.POINTER(Problem), C.POINTER(FwdOut), C.c_void_p]),
     "acattn_unnorm_attention_bwd": (C.c_int, [C.POINTER(Problem), C.POINTER(BwdIO), C.c_void_p]),
+    "acattn_timeaware_attention_supported": (C.c_int, [C.POINTER(Problem), C.POINTER(TimeExt)]),
+    "acattn_timeaware_attention_fwd": (C.c_int, [C.POINTER(Problem), C.POINTER(TimeExt), C.POINTER(FwdOut), C.c_void_p]),
+    "acattn_timeaware_attention_bwd": (C.c_int, [C.POINTER(Problem), C.POINTER(TimeExt), C.POINTER(BwdIO), C.POINTER(TimeGrads),
+                                                C.c_void_p]),
+    "acattn_time_rng_materialize": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_float, _f, _f, C.c_void_p]),
     "acattn_spatial_attention_bwd": (C.c_int, [C.POINTER(Problem), C.POINTER(SpatialBwdIO), C.c_void_p]),
     "acattn_spatial_attention_bwd_workspace_bytes": (C.c_int64, [C.POINTER(Problem)]),
     "acattn_spatial_affines": (C.c_int, [C.POINTER(Problem), _f, C.c_void_p]),

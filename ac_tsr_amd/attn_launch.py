@@ -293,3 +293,64 @@ def unnorm_attention_bwd_launch(lib, prob, q, n_heads: int, M, stats, *, d_att=N
     io.dgate_logits = _ptr(dgate_part)
     _lib.check(lib.acattn_unnorm_attention_bwd(C.byref(prob), C.byref(io), _stream()), "unnorm_attention_bwd")
     return dq, dk, dv, dqa, dka, dgate_part, part
+
+
+def fill_time_ext(pos_k, pos_v, time_index, time_k, time_v, p_time: float, *, keep_k=None, keep_v=None, seed: int = 0,
+                  seed_tensor=None) -> _lib.TimeExt:
+    """acattn_time_ext from checked tensors (pos_k / pos_v [B,L,H] already dropped, time_index int32 [B,L,L], the two
+    [time_span + 1, H] tables).  keep_k / keep_v (uint8 [B,L,L,H]) select explicit time-dropout bits; without them and with
+    p_time > 0 the kernels draw the counter stream of `seed` (+ *seed_tensor).  The caller keeps the tensors alive."""
+    t = _lib.TimeExt()
+    t.pos_k, t.pos_v, t.time_index, t.time_k, t.time_v = _ptr(pos_k), _ptr(pos_v), _ptr(time_index), _ptr(time_k), _ptr(time_v)
+    t.time_span, t.p_time = time_k.shape[0] - 1, float(p_time)
+    t.keep_time_k, t.keep_time_v = _ptr(keep_k), _ptr(keep_v)
+    t.time_seed, t.time_seed_device = seed & 0xFFFFFFFFFFFFFFFF, _ptr(seed_tensor)
+    return t
+
+
+def timeaware_attention_supported(lib, prob, text) -> bool:
+    """acattn_timeaware_attention_supported: does csrc/acattn_timeaware.hip cover this configuration?  (acattn_last_error
+    names the limit when not.)"""
+    return bool(lib.acattn_timeaware_attention_supported(C.byref(prob), C.byref(text)))
+
+
+def timeaware_attention_fwd_launch(lib, prob, text, q, n_heads: int, *, want_penalty: bool, poison: bool = False):
+    """One acattn_timeaware_attention_fwd call (ACTiSASRec's core).  Returns (ctx_attacked, ctx_calibrated, M, row_stats,
+    penalty_part or None)."""
+    B, L, H = q.shape
+    new = allocator(q, poison or POISON)
+    out = _lib.FwdOut()
+    ctx_att, ctx_cal, M, stats = new(B, L, H), new(B, L, H), new(B, n_heads, L, L), new(B, n_heads, L, _lib.NSTAT)
+    out.ctx_attacked, out.ctx_calibrated, out.attack_mask, out.row_stats = _ptr(ctx_att), _ptr(ctx_cal), _ptr(M), _ptr(stats)
+    pen = None
+    if want_penalty:
+        pen = new(B, n_heads, (L + 15) // 16)
+        out.penalty_part = _ptr(pen)
+    _lib.check(lib.acattn_timeaware_attention_fwd(C.byref(prob), C.byref(text), C.byref(out), _stream()),
+               "timeaware_attention_fwd")
+    return ctx_att, ctx_cal, M, stats, pen
+
+
+def timeaware_attention_bwd_launch(lib, prob, text, q, n_heads: int, M, stats, n_table_rows: int, *, d_att=None, d_cal=None,
+                                   d_M=None, d_pen=None, poison: bool = False):
+    """One acattn_timeaware_attention_bwd call: allocates the gradients, the parameter partials and the second launch's
+    workspace.  Returns (dq, dk, dv, dqa, dka, dgate_part [B,n_heads,L,L], part, d_pos_k, d_time_k, d_time_v); d pos_v is dv.
+    The table gradients are the kernel's true derivatives, row 0 included."""
+    B, L, H = q.shape
+    new = allocator(q, poison or POISON)
+    io = _lib.BwdIO()
+    io.attack_mask, io.row_stats = _ptr(M), _ptr(stats)
+    io.d_ctx_attacked, io.d_ctx_calibrated, io.d_attack_mask = _ptr(d_att), _ptr(d_cal), _ptr(d_M)
+    io.d_penalty_part = _ptr(d_pen)
+    dq, dk, dv, dqa, dka = (new(B, L, H) for _ in range(5))
+    io.dq, io.dk, io.dv, io.dqa, io.dka = _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dqa), _ptr(dka)
+    part = partials(io, q, n_heads, new)
+    dgate_part = new(B, n_heads, L, L)
+    io.dgate_logits = _ptr(dgate_part)
+    g = _lib.TimeGrads()
+    d_pos_k, d_time_k, d_time_v = new(B, L, H), new(n_table_rows, H), new(n_table_rows, H)
+    ws = new(3, B, n_heads, L, L)
+    g.d_pos_k, g.d_time_k, g.d_time_v, g.workspace = _ptr(d_pos_k), _ptr(d_time_k), _ptr(d_time_v), _ptr(ws)
+    _lib.check(lib.acattn_timeaware_attention_bwd(C.byref(prob), C.byref(text), C.byref(io), C.byref(g), _stream()),
+               "timeaware_attention_bwd")
+    return dq, dk, dv, dqa, dka, dgate_part, part, d_pos_k, d_time_k, d_time_v

@@ -70,9 +70,51 @@ int acattn_unnorm_supported(const acattn_problem& p);
 int acattn_launch_unnorm_fwd(const acattn_problem& p, const acattn_fwd_out& o, hipStream_t stream);
 int acattn_launch_unnorm_bwd(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream);
 
+// acattn_timeaware.hip: the time-interval core of ACTiSASRec (validation included, as above)
+int acattn_timeaware_supported(const acattn_problem& p, const acattn_time_ext& t, const char** why);
+int acattn_launch_timeaware_fwd(const acattn_problem& p, const acattn_time_ext& t, const acattn_fwd_out& o, hipStream_t stream);
+int acattn_launch_timeaware_bwd(const acattn_problem& p, const acattn_time_ext& t, const acattn_bwd_io& io,
+                                const acattn_time_grads& g, hipStream_t stream);
+int acattn_launch_time_rng(int B, int L, int H, uint64_t seed, float p, uint8_t* keep_k, uint8_t* keep_v, hipStream_t stream);
+
 extern "C" {
 
 int acattn_abi_version(void) { return ACATTN_ABI_VERSION; }
+
+int acattn_timeaware_attention_supported(const acattn_problem* p, const acattn_time_ext* t) {
+  if (!p || !t) return 0;
+  const char* why = nullptr;
+  const int ok = acattn_timeaware_supported(*p, *t, &why);
+  if (!ok) snprintf(g_err, sizeof(g_err), "%s", why);
+  return ok;
+}
+
+int acattn_timeaware_attention_fwd(const acattn_problem* p, const acattn_time_ext* t, const acattn_fwd_out* out, void* stream) {
+  if (!p || !t || !out) return fail("problem, time and out must be non-NULL");
+  int rc = acattn_launch_timeaware_fwd(*p, *t, *out, (hipStream_t)stream);
+  if (rc == 0 && out->penalty_part)
+    rc = acattn_launch_penalty_rows(out->attack_mask, p->B, p->n_heads, p->L, out->penalty_part, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
+int acattn_timeaware_attention_bwd(const acattn_problem* p, const acattn_time_ext* t, const acattn_bwd_io* io,
+                                   const acattn_time_grads* grads, void* stream) {
+  if (!p || !t || !io || !grads) return fail("problem, time, io and grads must be non-NULL");
+  const int rc = acattn_launch_timeaware_bwd(*p, *t, *io, *grads, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
+int acattn_time_rng_materialize(int32_t B, int32_t L, int32_t H, uint64_t seed, float p, uint8_t* keep_k, uint8_t* keep_v,
+                                void* stream) {
+  if (B < 1 || L < 1 || H < 1) return fail("B, L, H must be positive");
+  if (!(p >= 0.f && p < 1.f)) return fail("p must lie in [0, 1)");
+  if ((int64_t)B * L * L * 2 * ((H + 31) / 32) >= (1LL << 32)) return fail("B L L H / 16 must stay below 2^32 (the time dropout's counter)");
+  const int rc = acattn_launch_time_rng(B, L, H, seed, p, keep_k, keep_v, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
 
 int acattn_unnorm_attention_supported(const acattn_problem* p) { return p ? acattn_unnorm_supported(*p) : 0; }
 

@@ -179,6 +179,10 @@ class AttackRTransformerLayer(nn.Module):
                                two_level=self.two_level, rich_calibrated_combine=self.rich_calibrated_combine,
                                adversarial=self.adversarial, anneal_rate=rate, renormalise=self.renormalise)
 
+    def _attention_core(self, mq, mk, mv, qa, ka, gate_logits, attention_mask, cfg, **kw):
+        """The one HIP call between the projections and the tails (ACTimeAwareTransformerLayer has another core)."""
+        return ops.calibrated_attention(mq, mk, mv, qa, ka, gate_logits, attention_mask, cfg, **kw)
+
     def forward(self, hidden_states, attention_mask, return_attention_prob=False, return_all_attention_prob=False,
                 _rnd=None, _need_attacked=True, _attack_upstream=True, _rows=None, _planes=None):
         """`_need_attacked=False` (set by the encoder for layers whose attacked output nobody can observe) skips the
@@ -209,7 +213,7 @@ class AttackRTransformerLayer(nn.Module):
                                           keep_before=getattr(_rnd, "keep_before", None))
         p_drop = att.attn_dropout_prob if (self.training or (core_rnd is not None and core_rnd.keep_after is not None)) else 0.0
         want_probs = return_all_attention_prob or return_attention_prob
-        ctx_att, ctx_cal, attack_mask, probs = ops.calibrated_attention(
+        ctx_att, ctx_cal, attack_mask, probs = self._attention_core(
             mq, mk, mv, qa, ka, gate_logits, attention_mask, cfg, p_drop=p_drop, rnd=core_rnd, want_probs=want_probs,
             seed_tensor=state_of(self).seed_tensor if core_rnd is None else None, read_rows=_rows,
             attack_upstream=_attack_upstream, state=state_of(self), rich_ratio=getattr(self, "rich_calibrated_combine_ratio", None),
@@ -370,4 +374,82 @@ class AttackRTransformerEncoder(nn.Module):
             return all_encoder_layers, all_attack_masks, all_probs
         if return_attention_prob:
             return all_encoder_layers, all_attack_masks, all_attention_prob
+        return all_encoder_layers, all_attack_masks
+
+
+class ACTimeAwareTransformerLayer(AttackRTransformerLayer):
+    """recbole/model/transformer_layers.py:1232-1327 (ACTimeAwareTransformerLayer over ACTimeAwareMultiHeadAttention,
+    :1010-1180): the un-normalised layer whose scores and value sums carry an absolute-position row per key and a
+    time-interval row per pair.  Reference constructor arguments and state-dict keys (attack_attention.*, gate,
+    feed_forward.*); the reference pins the gate to 50 positions (:1265), `seq_length` (not a reference argument) opens it.
+    Projections, split planes, tails, pruning and `_rows` work as in AttackRTransformerLayer(renormalise=False); the core is
+    csrc/acattn_timeaware.hip ('gate', two-level, L <= 64: anything else raises a ValueError that names the limit)."""
+
+    def __init__(self, n_heads, hidden_size, intermediate_size, hidden_dropout_prob, attn_dropout_prob, hidden_act,
+                 layer_norm_eps, combine_option='fixed', use_order=True, use_distance=True, two_level=True,
+                 rich_calibrated_combine='fixed', seq_length=50):
+        super().__init__(n_heads, hidden_size, intermediate_size, hidden_dropout_prob, attn_dropout_prob, hidden_act,
+                         layer_norm_eps, combine_option, use_order=use_order, use_distance=use_distance, two_level=two_level,
+                         rich_calibrated_combine=rich_calibrated_combine, seq_length=seq_length, renormalise=False)
+        self._time_args = None
+
+    def _attention_core(self, mq, mk, mv, qa, ka, gate_logits, attention_mask, cfg, *, p_drop, rnd, seed_tensor, attack_upstream,
+                        state, gate_is_prob=False, w_order=None, b_order=None, w_dist=None, b_dist=None, scalar=None, **_unused):
+        pos_k, pos_v, time_k, time_v = self._time_args
+        return ops.timeaware_attention(mq, mk, mv, qa, ka, gate_logits, attention_mask, cfg, w_order=w_order, b_order=b_order,
+                                       w_dist=w_dist, b_dist=b_dist, scalar=scalar, pos_k=pos_k, pos_v=pos_v, time_k=time_k,
+                                       time_v=time_v, p_drop=p_drop, rnd=rnd, seed_tensor=seed_tensor,
+                                       attack_upstream=attack_upstream, state=state, gate_is_prob=gate_is_prob)
+
+    def forward(self, hidden_states, attention_mask, absolute_pos_K, absolute_pos_V, time_matrix_emb_K, time_matrix_emb_V,
+                return_attention_prob=False, _rnd=None, _need_attacked=True, _attack_upstream=True, _rows=None, _planes=None):
+        """absolute_pos_K / _V: the dropped position rows [B,L,H]; time_matrix_emb_K / _V: ops.TimeIntervals handles (table,
+        index matrix, keep bits or seed) in place of the reference's [B,L,L,H] tensors.  Returns (attacked, calibrated, M)."""
+        if return_attention_prob:
+            raise ValueError("the time-interval attention core has no probability dumps (return_attention_prob)")
+        self._time_args = (absolute_pos_K, absolute_pos_V, time_matrix_emb_K, time_matrix_emb_V)
+        try:
+            outs = super().forward(hidden_states, attention_mask, _rnd=_rnd, _need_attacked=_need_attacked,
+                                   _attack_upstream=_attack_upstream, _rows=_rows, _planes=_planes)
+        finally:
+            self._time_args = None
+        return outs[:3]
+
+
+class ACTimeAwareTransformerEncoder(nn.Module):
+    """recbole/model/transformer_layers.py:1330-1422."""
+
+    def __init__(self, n_layers=2, n_heads=2, hidden_size=64, inner_size=256, hidden_dropout_prob=0.5,
+                 attn_dropout_prob=0.5, hidden_act='gelu', layer_norm_eps=1e-12, combine_option='fixed', use_order=True,
+                 use_distance=True, two_level=True, rich_calibrated_combine='fixed', seq_length=50):
+        super().__init__()
+        layer = ACTimeAwareTransformerLayer(
+            n_heads, hidden_size, inner_size, hidden_dropout_prob, attn_dropout_prob, hidden_act, layer_norm_eps,
+            combine_option, use_order=use_order, use_distance=use_distance, two_level=two_level,
+            rich_calibrated_combine=rich_calibrated_combine, seq_length=seq_length)
+        self.layer = nn.ModuleList([copy.deepcopy(layer) for _ in range(n_layers)])
+
+    def forward(self, hidden_states, attention_mask, absolute_pos_K, absolute_pos_V, time_matrix_emb_K, time_matrix_emb_V,
+                output_all_encoded_layers=True, return_attention_prob=False, _rnds: Optional[List] = None, _last_rows=None):
+        """attention_mask: an `ops.StructuredMask`.  `_last_rows` as in AttackRTransformerEncoder.forward."""
+        if _last_rows is not None and output_all_encoded_layers:
+            raise ValueError("_last_rows needs output_all_encoded_layers=False")
+        all_encoder_layers, all_attack_masks = [], []
+        attacked_hidden_states = calibrated_hidden_states = None
+        layer_planes = planes_mod.make(list(self.layer), hidden_states, _last_rows)
+        for layer_idx, layer_module in enumerate(self.layer):
+            last = layer_idx == len(self.layer) - 1
+            attacked_hidden_states, calibrated_hidden_states, attack_mask = layer_module(
+                hidden_states, attention_mask, absolute_pos_K, absolute_pos_V, time_matrix_emb_K, time_matrix_emb_V,
+                return_attention_prob, _rnd=_rnds[layer_idx] if _rnds is not None else None,
+                _need_attacked=output_all_encoded_layers or last,
+                # the time tables and position rows are no attack transforms: the first layer owes them nothing in pass 2
+                _attack_upstream=layer_idx > 0 or not state_of(self).prune_dead_work,
+                _rows=_last_rows if last else None, _planes=layer_planes[layer_idx])
+            hidden_states = calibrated_hidden_states  # transformer_layers.py:1409
+            all_attack_masks.append(attack_mask)
+            if output_all_encoded_layers:
+                all_encoder_layers.append((attacked_hidden_states, calibrated_hidden_states))
+        if not output_all_encoded_layers:
+            all_encoder_layers.append((attacked_hidden_states, calibrated_hidden_states))
         return all_encoder_layers, all_attack_masks

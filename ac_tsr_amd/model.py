@@ -20,7 +20,7 @@ from . import layers
 from .layers import AttackRTransformerEncoder
 from . import ce, fused_embed, fused_embed_user
 from .linear import embedding_lookup, full_sort_scores
-from .ops import StructuredMask, mask_penalty
+from .ops import StructuredMask, TimeIntervals, mask_penalty
 from .state import StepState
 
 
@@ -398,6 +398,144 @@ class ACSSEPT(SequentialRecommender):
         table, Di = self.item_embedding.weight, self.item_hidden_size
         score = lambda out: torch.matmul(out[:, :Di], table.transpose(0, 1)) + self._user_test_term(out, user_id).unsqueeze(1)
         return score(attacked_output), score(calibrated_output)
+
+
+class ACTiSASRec(SequentialRecommender):
+    """recbole/model/sequential_recommender/actisasrec.py:22-224: SASRec with time-interval attention (TiSASRec) over the
+    calibrated encoder of recbole/model/transformer_layers.py:1010-1422 (layers.ACTimeAwareTransformerEncoder;
+    csrc/acattn_timeaware.hip: 'gate', two-level, MAX_ITEM_LIST_LENGTH <= 64).  Same constructor, config keys (`time_span`,
+    `TIME_FIELD`; `use_position_embedding` is read and unused, as in the reference), attribute names, methods, return values
+    and state-dict keys.  The two [B,L,L,H] tensors of actisasrec.py:113-114, 123-124 are never built: the encoder gets the
+    tables, the index matrix and the dropout as handles (ops.TimeIntervals)."""
+
+    renormalise = False  # (the trainer asks: neither graph capture nor the one-walk combined backward is built for this core)
+
+    def __init__(self, config, dataset):
+        super().__init__(config, dataset)
+        self.n_layers = config['n_layers']
+        self.n_heads = config['n_heads']
+        self.hidden_size = config['hidden_size']
+        self.inner_size = config['inner_size']
+        self.hidden_dropout_prob = config['hidden_dropout_prob']
+        self.attn_dropout_prob = config['attn_dropout_prob']
+        self.hidden_act = config['hidden_act']
+        self.layer_norm_eps = config['layer_norm_eps']
+        self.time_span = config['time_span']
+        self.timestamp = _cfg(config, 'TIME_FIELD', 'timestamp') + '_list'
+        self.initializer_range = config['initializer_range']
+        self.loss_type = config['loss_type']
+        self.combine_option = config['combine_option']
+        self.rich_calibrated_combine = _cfg(config, 'rich_calibrated_combine')
+        self.two_level = _cfg(config, 'two_level')
+        self.use_position_embedding = _cfg(config, 'use_position_embedding')
+        self.use_order = _cfg(config, 'use_order')
+        self.use_distance = _cfg(config, 'use_distance')
+        self.trainable_mask_loss_weight = _cfg(config, 'trainable_mask_loss_weight')
+        self.dp_mask_penalty = 'local'
+        seq_length = _cfg(config, 'gate_seq_length', 50)  # the reference pins the gate to 50 (transformer_layers.py:1265)
+
+        self.item_embedding = nn.Embedding(self.n_items, self.hidden_size, padding_idx=0)
+        self.absolute_pos_K_embedding = nn.Embedding(self.max_seq_length, self.hidden_size, padding_idx=0)
+        self.absolute_pos_V_embedding = nn.Embedding(self.max_seq_length, self.hidden_size, padding_idx=0)
+        self.time_matrix_emb_K_embedding = nn.Embedding(self.time_span + 1, self.hidden_size, padding_idx=0)
+        self.time_matrix_emb_V_embedding = nn.Embedding(self.time_span + 1, self.hidden_size, padding_idx=0)
+        self.ti_trm_encoder = layers.ACTimeAwareTransformerEncoder(
+            n_layers=self.n_layers, n_heads=self.n_heads, hidden_size=self.hidden_size, inner_size=self.inner_size,
+            hidden_dropout_prob=self.hidden_dropout_prob, attn_dropout_prob=self.attn_dropout_prob,
+            hidden_act=self.hidden_act, layer_norm_eps=self.layer_norm_eps, combine_option=self.combine_option,
+            use_order=self.use_order, use_distance=self.use_distance, two_level=self.two_level,
+            rich_calibrated_combine=self.rich_calibrated_combine, seq_length=seq_length)
+        self.LayerNorm = nn.LayerNorm(self.hidden_size, eps=self.layer_norm_eps)
+        self.dropout = nn.Dropout(self.hidden_dropout_prob)
+        if self.trainable_mask_loss_weight:
+            self.mask_loss_weight = nn.Parameter(torch.FloatTensor([0.3]), requires_grad=True)
+        else:
+            self.mask_loss_weight = config['mask_loss_weight']
+        if self.loss_type == 'BPR':
+            self.loss_fct = _BPRLoss()
+        elif self.loss_type == 'CE':
+            self.loss_fct = nn.CrossEntropyLoss()
+        else:
+            raise NotImplementedError("Make sure 'loss_type' in ['BPR', 'CE']!")
+        self.apply(self._init_weights)  # (overwrites row 0 of the five padded tables too, as the reference's does)
+        self.step_state = StepState().attach(self)
+
+    _init_weights = ACSASRec._init_weights
+    _cal_loss = ACSASRec._cal_loss
+
+    def get_time_matrix(self, time_seq):
+        """actisasrec.py:148-157, the same ops: [B, L] stamps -> int32 [B, L, L], |t_i - t_j| clipped at time_span."""
+        time_matrix_i = time_seq.unsqueeze(-1).expand([-1, self.max_seq_length, self.max_seq_length])
+        time_matrix_j = time_seq.unsqueeze(1).expand([-1, self.max_seq_length, self.max_seq_length])
+        time_matrix = torch.abs(time_matrix_i - time_matrix_j)
+        max_time_matrix = (torch.ones_like(time_matrix) * self.time_span).to(time_matrix.device)
+        return torch.where(time_matrix > self.time_span, max_time_matrix, time_matrix).int()
+
+    def _dropped(self, x, keep):
+        if keep is not None:
+            return x * (keep.to(x.dtype) / (1.0 - self.dropout.p))
+        return self.dropout(x)
+
+    def forward(self, item_seq, item_seq_len, time_matrix, _rnds=None, _keep_emb=None, _keep_pos=None, _keep_time=None,
+                _last_row=None):
+        """actisasrec.py:106-141 -> (attacked [B,H], calibrated [B,H], attack masks).  `_keep_pos` / `_keep_time`: explicit
+        (K, V) keep masks of the two position dropouts ([B,L,H]) and the two time dropouts ([B,L,L,H])."""
+        position_ids = torch.arange(item_seq.size(1), dtype=torch.long, device=item_seq.device).unsqueeze(0).expand_as(item_seq)
+        kp_k, kp_v = _keep_pos if _keep_pos is not None else (None, None)
+        absolute_pos_K = self._dropped(self.absolute_pos_K_embedding(position_ids), kp_k).contiguous()
+        absolute_pos_V = self._dropped(self.absolute_pos_V_embedding(position_ids), kp_v).contiguous()
+        if item_seq.is_cuda and fused_embed.supported(self.hidden_size):
+            input_emb, nonzero = fused_embed.embed_layer_norm(item_seq, self.item_embedding, None, self.LayerNorm, self.dropout.p,
+                                                              self.training, _keep_emb, return_nonzero=True)
+            mask = StructuredMask(key_valid=nonzero, causal=True)
+        else:
+            input_emb = self._dropped(self.LayerNorm(embedding_lookup(item_seq, self.item_embedding)), _keep_emb)
+            mask = self.get_structured_mask(item_seq)
+        # the two time dropouts (actisasrec.py:123-124) are drawn once per forward: one seed, shared by every layer
+        kt_k, kt_v = _keep_time if _keep_time is not None else (None, None)
+        p_time = self.dropout.p if (self.training or kt_k is not None) else 0.0
+        seed = self.step_state.draw_seed() if (p_time > 0 and kt_k is None) else 0
+        index = time_matrix.to(torch.int32).contiguous()
+        as_bits = lambda t: None if t is None else t.to(torch.uint8).contiguous()
+        handle = lambda emb, keep: TimeIntervals(emb.weight, index, p_time, as_bits(keep), seed,
+                                                 self.step_state.seed_tensor if keep is None else None)
+        time_K = handle(self.time_matrix_emb_K_embedding, kt_k)
+        time_V = handle(self.time_matrix_emb_V_embedding, kt_v)
+        if not self.step_state.prune_dead_work:  # the reference's full schedule (actisasrec.py:128-140)
+            trm_output = self.ti_trm_encoder(input_emb, mask, absolute_pos_K, absolute_pos_V, time_K, time_V,
+                                             output_all_encoded_layers=True, _rnds=_rnds)
+            attacked_output, calibrated_output = trm_output[0][-1]
+            return (self.gather_indexes(attacked_output, item_seq_len - 1),
+                    self.gather_indexes(calibrated_output, item_seq_len - 1), trm_output[1])
+        last = (item_seq_len - 1).view(-1, 1) if _last_row is None else _last_row.view(-1, 1)
+        trm_output = self.ti_trm_encoder(input_emb, mask, absolute_pos_K, absolute_pos_V, time_K, time_V,
+                                         output_all_encoded_layers=False, _rnds=_rnds, _last_rows=last)
+        attacked_output, calibrated_output = trm_output[0][-1]
+        return attacked_output.squeeze(1), calibrated_output.squeeze(1), trm_output[1]
+
+    def _outputs(self, interaction, **kw):
+        time_matrix = self.get_time_matrix(interaction[self.timestamp])
+        return self.forward(interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN], time_matrix, **kw)
+
+    def calculate_loss(self, interaction, _rnds=None, _keep_emb=None, _keep_pos=None, _keep_time=None):
+        """actisasrec.py:175-195 -> (final_attacked_loss, calibrated_loss)."""
+        attacked_output, calibrated_output, all_attack_masks = self._outputs(
+            interaction, _rnds=_rnds, _keep_emb=_keep_emb, _keep_pos=_keep_pos, _keep_time=_keep_time)
+        attacked_loss = -self._cal_loss(attacked_output, interaction, attack_loss=True)
+        calibrated_loss = self._cal_loss(calibrated_output, interaction)
+        mask_penalty = torch.mean(torch.stack([_penalty(m) for m in all_attack_masks], dim=0))
+        weight = self.mask_loss_weight[0] if self.trainable_mask_loss_weight else self.mask_loss_weight
+        return attacked_loss + mask_penalty * weight, calibrated_loss
+
+    def predict(self, interaction):
+        attacked_output, calibrated_output, _ = self._outputs(interaction)
+        test_item_emb = self.item_embedding(interaction[self.ITEM_ID])
+        return torch.mul(attacked_output, test_item_emb).sum(dim=1), torch.mul(calibrated_output, test_item_emb).sum(dim=1)
+
+    def full_sort_predict(self, interaction, _rnds=None):
+        attacked_output, calibrated_output, _ = self._outputs(interaction, _rnds=_rnds)
+        table = self.item_embedding.weight.transpose(0, 1)
+        return torch.matmul(attacked_output, table), torch.matmul(calibrated_output, table)
 
 
 class AcBERT4Rec(SequentialRecommender):

@@ -426,6 +426,163 @@ class _UnnormalisedAttention(torch.autograd.Function):
         return tuple(grads[:11]) + (None,) * 10
 
 
+@dataclass
+class TimeIntervals:
+    """One of the two time-interval arguments of ACTimeAwareTransformerLayer.forward (time_matrix_emb_K / _V,
+    transformer_layers.py:1285-1287) as a handle instead of the reference's gathered and dropped [B,L,L,H] tensor: the
+    [time_span + 1, H] table, the index matrix of get_time_matrix (int32 [B,L,L], shared by both handles) and the dropout of
+    actisasrec.py:123-124 as a rate plus explicit keep bits (uint8 [B,L,L,H]) or the counter seed all layers of one forward
+    share.  The kernels gather the rows and replay the bits (csrc/acattn_timeaware.hip)."""
+
+    table: torch.Tensor
+    index: torch.Tensor
+    p_drop: float = 0.0
+    keep: Optional[torch.Tensor] = None
+    seed: int = 0
+    seed_tensor: Optional[torch.Tensor] = None
+
+
+TIMEAWARE_MAX_L = 64  # csrc/acattn_timeaware.hip holds a query block's row of four key tiles
+TIMEAWARE_LDS_BYTES = 160 * 1024  # the two gradient tables of one head live in one workgroup's LDS
+
+
+def _check_timeaware(q, k, v, qa, ka, gate_logits, mask, cfg: AttentionConfig, w_order, w_dist, pos_k, pos_v,
+                     time_k: TimeIntervals, time_v: TimeIntervals):
+    """ValueError naming the limit for everything csrc/acattn_timeaware.hip does not take (include/acattn.h:
+    acattn_timeaware_attention_supported); there is no other kernel to fall back to."""
+    what = "time-interval attention (ACTiSASRec)"
+    if not cfg.adversarial:
+        raise ValueError(f"{what} needs the adversarial calibrator (adversarial=True)")
+    if cfg.combine_option != "gate":
+        raise ValueError(f"{what} is built for combine_option 'gate' only, not {cfg.combine_option!r}")
+    if not cfg.two_level:
+        raise ValueError(f"{what} is built for two_level=True only (the one-level form is not)")
+    if not isinstance(mask, StructuredMask):
+        raise ValueError(f"{what} takes a StructuredMask only; dense masks are not built")
+    if w_order is None or w_dist is None:
+        raise ValueError(f"{what} needs both spatial terms (order and distance)")
+    for name, t in (("q", q), ("k", k), ("v", v), ("qa", qa), ("ka", ka), ("gate_logits", gate_logits),
+                    ("key_valid", mask.key_valid), ("pos_k", pos_k), ("pos_v", pos_v), ("time_k.table", time_k.table),
+                    ("time_v.table", time_v.table), ("time index", time_k.index)):
+        if t is None or not t.is_cuda:
+            raise ValueError(f"{what}: {name} must be a tensor on the GPU (HIP kernels only, no CPU path)")
+    B, L, H = q.shape
+    if L > TIMEAWARE_MAX_L:
+        raise ValueError(f"{what} is built for sequence length L <= {TIMEAWARE_MAX_L}, got {L}")
+    if H % cfg.n_heads or H // cfg.n_heads not in (16, 32, 64):
+        raise ValueError(f"{what} is built for head sizes 16, 32 and 64, got hidden {H} / {cfg.n_heads} heads")
+    if time_v.index is not time_k.index and time_v.index.data_ptr() != time_k.index.data_ptr():
+        raise ValueError(f"{what}: both time handles must share one index matrix")
+    if time_k.index.dtype != torch.int32 or time_k.index.shape != (B, L, L) or not time_k.index.is_contiguous():
+        raise ValueError(f"{what}: the time index must be a contiguous int32 [B, L, L] tensor (get_time_matrix)")
+    rows = time_k.table.shape[0]
+    if time_k.table.shape != (rows, H) or time_v.table.shape != (rows, H):
+        raise ValueError(f"{what}: both time tables must be [time_span + 1, {H}]")
+    if rows < 2 or 8 * rows * (H // cfg.n_heads) > TIMEAWARE_LDS_BYTES:
+        raise ValueError(f"{what} is built for 1 <= time_span with 8 (time_span + 1) head_size <= 160 KiB, got time_span {rows - 1} "
+                         f"at head size {H // cfg.n_heads}")
+    if pos_k.shape != (B, L, H) or pos_v.shape != (B, L, H):
+        raise ValueError(f"{what}: pos_k and pos_v must be [B, L, H]")
+    if (time_k.p_drop, time_k.seed, time_k.keep is None) != (time_v.p_drop, time_v.seed, time_v.keep is None):
+        raise ValueError(f"{what}: both time handles must carry the same dropout rate, seed and kind of keep bits")
+    for t in (time_k.keep, time_v.keep):
+        if t is not None and (t.dtype != torch.uint8 or t.shape != (B, L, L, H) or not t.is_cuda):
+            raise ValueError(f"{what}: explicit time keep bits must be uint8 [B, L, L, H] on the GPU")
+
+
+def _time_ext(pos_k, pos_v, time_k: TimeIntervals, time_v: TimeIntervals):
+    for name, t in (("pos_k", pos_k), ("pos_v", pos_v), ("time_k", time_k.table), ("time_v", time_v.table)):
+        _need_cuda(name, t)
+    return attn_launch.fill_time_ext(pos_k, pos_v, time_k.index, time_k.table, time_v.table, time_k.p_drop, keep_k=time_k.keep,
+                                     keep_v=time_v.keep, seed=time_k.seed, seed_tensor=time_k.seed_tensor)
+
+
+class _TimeAwareAttention(torch.autograd.Function):
+    """ACTiSASRec's attention core (csrc/acattn_timeaware.hip) on the attn_launch path.  The first 15 inputs can carry
+    gradients (q, k, v, qa, ka, gate logits, the five calibrator parameters, pos_k, pos_v, the two time tables).
+    Outputs (ctx_attacked, ctx_calibrated, M, penalty rows or None)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar, pos_k, pos_v, table_k, table_v,
+                mask, cfg: AttentionConfig, p_drop: float, rnd, seed: int, time_k: TimeIntervals, time_v: TimeIntervals,
+                seed_tensor=None, attack_upstream=True, state=_DEFAULT_STATE, gate_is_prob=False):
+        lib = _lib.load()
+        ctx.set_materialize_grads(False)
+        keep = []
+        prob = _fill_problem(q, k, v, qa, ka, gate_logits, mask, w_order.reshape(-1), b_order, w_dist.reshape(-1), b_dist,
+                             scalar, None, cfg, p_drop, rnd, seed, keep, seed_tensor, gate_is_prob)
+        text = _time_ext(pos_k, pos_v, time_k, time_v)
+        if not attn_launch.timeaware_attention_supported(lib, prob, text):
+            raise ValueError("time-interval attention: " + lib.acattn_last_error().decode())
+        want_pen = bool(PENALTY_ROWS and any(ctx.needs_input_grad[:15]))
+        ctx_att, ctx_cal, M, stats, pen = attn_launch.timeaware_attention_fwd_launch(lib, prob, text, q, cfg.n_heads,
+                                                                                    want_penalty=want_pen)
+        ctx.cfg, ctx.p_drop, ctx.rnd, ctx.seed, ctx.mask, ctx.seed_tensor = cfg, p_drop, rnd, seed, mask, seed_tensor
+        ctx.gate_is_prob, ctx.attack_upstream, ctx.state, ctx.time = gate_is_prob, attack_upstream, state, (time_k, time_v)
+        ctx.save_for_backward(q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar, pos_k, pos_v, table_k,
+                              table_v, M, stats)
+        return ctx_att, ctx_cal, M, pen
+
+    @staticmethod
+    def backward(ctx, d_att, d_cal, d_M, d_pen):
+        # Never mutates saved state: the trainer walks this node twice (retain_graph=True, recbole/trainer/trainer.py:677,684).
+        (q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar, pos_k, pos_v, table_k, table_v, M,
+         stats) = ctx.saved_tensors
+        cfg = ctx.cfg
+        lib = _lib.load()
+        keep = []
+        d_att, d_cal, d_M, d_pen = (None if t is None else t.contiguous() for t in (d_att, d_cal, d_M, d_pen))
+        attack_only = ctx.state.attack_pass_only and not ctx.attack_upstream
+        prob = _fill_problem(q, k, v, qa, ka, gate_logits, ctx.mask, w_order.reshape(-1), b_order, w_dist.reshape(-1), b_dist,
+                             scalar, None, cfg, ctx.p_drop, ctx.rnd, ctx.seed, keep, ctx.seed_tensor, ctx.gate_is_prob)
+        text = _time_ext(pos_k, pos_v, *ctx.time)
+        res = attn_launch.timeaware_attention_bwd_launch(lib, prob, text, q, cfg.n_heads, M, stats, table_k.shape[0], d_att=d_att,
+                                                         d_cal=d_cal, d_M=d_M, d_pen=d_pen)
+        grads = _CalibratedAttention._finish_backward(lib, attack_only, *res[:7], q.shape[2] // cfg.n_heads, w_order, b_order,
+                                                      w_dist, b_dist, scalar, None, ctx.state)
+        if attack_only:  # pass 2 keeps only the attack transforms' gradients
+            return tuple(grads[:11]) + (None,) * 15
+        d_pos_k, d_time_k, d_time_v = res[7:]
+        # nn.Embedding(padding_idx=0): row 0 of both time tables is read like any other row and never trained
+        # (actisasrec.py:56-57); the kernel returns its true derivative
+        d_time_k[0].zero_()
+        d_time_v[0].zero_()
+        return tuple(grads[:11]) + (d_pos_k, res[2], d_time_k, d_time_v) + (None,) * 11
+
+
+def timeaware_attention(q, k, v, qa, ka, gate_logits, mask, cfg: AttentionConfig, *, w_order, b_order, w_dist, b_dist, scalar,
+                        pos_k, pos_v, time_k: TimeIntervals, time_v: TimeIntervals, p_drop: float = 0.0,
+                        rnd: Optional[ExplicitRandomness] = None, seed: Optional[int] = None,
+                        seed_tensor: Optional[torch.Tensor] = None, attack_upstream: bool = True, state=_DEFAULT_STATE,
+                        gate_is_prob: bool = False):
+    """Fused core of one ACTimeAwareTransformerLayer between the projections and the output dense
+    (recbole/model/transformer_layers.py:1107-1180, :1065-1090, :1296-1303).  pos_k / pos_v: the dropped absolute-position rows
+    [B,L,H]; time_k / time_v: TimeIntervals handles.  Gradients flow to q, k, v, qa, ka, the gate logits, the five
+    calibrator parameters, pos_k, pos_v and the two handles' tables (row 0 of the tables gets zeros: padding_idx).  Anything
+    outside the kernels' domain raises a ValueError that names the limit.
+
+    Returns (ctx_attacked [B,L,H], ctx_calibrated [B,L,H], M [B,h,L,L], {})."""
+    if rnd is None and seed is None:
+        seed = state.draw_seed()
+    _check_timeaware(q, k, v, qa, ka, gate_logits, mask, cfg, w_order, w_dist, pos_k, pos_v, time_k, time_v)
+    ctx_att, ctx_cal, M, pen = _TimeAwareAttention.apply(
+        q, k, v, qa, ka, gate_logits, w_order, b_order, w_dist, b_dist, scalar, pos_k, pos_v, time_k.table, time_v.table, mask,
+        cfg, p_drop, rnd, seed or 0, time_k, time_v, seed_tensor, attack_upstream, state, gate_is_prob)
+    if pen is not None:
+        M._acattn_pen = pen  # see PENALTY_ROWS
+    return ctx_att, ctx_cal, M, {}
+
+
+def materialize_time_randomness(B: int, L: int, H: int, seed: int, p_drop: float, device):
+    """The counter-mode keep bits of the two time dropouts for (seed, shape): (keep_k, keep_v), uint8 [B,L,L,H]
+    (acattn_time_rng_materialize)."""
+    lib = _lib.load()
+    keep_k, keep_v = (torch.empty(B, L, L, H, device=device, dtype=torch.uint8) for _ in range(2))
+    _lib.check(lib.acattn_time_rng_materialize(B, L, H, seed & 0xFFFFFFFFFFFFFFFF, p_drop, _ptr(keep_k), _ptr(keep_v), _stream()),
+               "time_rng_materialize")
+    return keep_k, keep_v
+
+
 def calibrated_attention(q, k, v, qa, ka, gate_logits, mask, cfg: AttentionConfig, *, w_order=None, b_order=None,
                          w_dist=None, b_dist=None, scalar=None, rich_ratio=None, p_drop: float = 0.0,
                          rnd: Optional[ExplicitRandomness] = None, seed: Optional[int] = None,

@@ -43,8 +43,8 @@ class AttackSASRecTrainer:
                              "with adversarial_calibrator=False has no attacked loss: use the default two-pass step "
                              "(its second pass is then empty)")
         if self.combined_backward and not getattr(model, 'renormalise', True):
-            raise ValueError("combined_backward=True is not built for a model on the un-normalised attention core (ACSSEPT: "
-                             "its autograd node has no backward_pair); use the default two-pass step")
+            raise ValueError("combined_backward=True is not built for a model on an un-normalised attention core (ACSSEPT, "
+                             "ACTiSASRec: their autograd nodes have no backward_pair); use the default two-pass step")
         if self.combined_backward:
             from .combined import instrument_package
             instrument_package()  # before any forward whose graph will be walked
@@ -233,7 +233,7 @@ class AttackSASRecTrainer:
         assert self.device.type == 'cuda'
         assert warmup >= 1, "at least one eager step must precede the capture (it creates the optimizer's state)"
         if not getattr(self.model, 'renormalise', True):
-            raise ValueError("a model on the un-normalised attention core (ACSSEPT) trains eagerly only: capturing its step "
+            raise ValueError("a model on an un-normalised attention core (ACSSEPT, ACTiSASRec) trains eagerly only: capturing its step "
                              "into a hipGraph is not supported yet (DESIGN.md section 4.11)")
         for m in self.model.modules():
             # 'annealing' advances a host-side step counter on every forward (recbole/model/layers.py:890-891) and the

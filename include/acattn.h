@@ -867,6 +867,74 @@ int acattn_unnorm_attention_supported(const acattn_problem* p);
 int acattn_unnorm_attention_fwd(const acattn_problem* p, const acattn_fwd_out* out, void* stream);
 int acattn_unnorm_attention_bwd(const acattn_problem* p, const acattn_bwd_io* io, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * [added within ABI 34: new entry points and two new structs only, every existing struct is unchanged] The TIME-INTERVAL
+ * attention core of ACTiSASRec (actisasrec.py:59 builds its encoder from
+ * recbole/model/transformer_layers.py:1010-1422).  The un-normalised core above (same mixtures, :1297-1303, no soft-max over
+ * them) with a per-key absolute-position term and a per-PAIR time-interval term in the scores and in the value sum.  Per head,
+ * with pk_j, pv_j the head's slices of the (already dropped) position rows, t_ij = time_index[b, i, j] and
+ * TK_ij = dropout(time_k[t_ij]), TV_ij = dropout(time_v[t_ij]) (head slices; actisasrec.py:113-114, :123-124):
+ *     S_ij = q_i.(k_j + pk_j) + q_i.TK_ij + e_order(q_i, k_j) + e_distance(q_i, k_j)      transformer_layers.py:1125-1166
+ *     P = dropout(softmax(S / sqrt(dh) + mask)),  M = dropout(softmax(qa.ka^T / sqrt(dh) + mask))      :1168-1176, :1065-1082
+ *     ctx_x[i] = sum_j A_x[i, j] (v_j + pv_j + TV_ij),   x in {attacked, calibrated}                   :1084-1090
+ * The reference gathers TK and TV as two [B,L,L,H] tensors per forward; here the kernels (csrc/acattn_timeaware.hip) gather
+ * the table rows where they need them and replay the dropout bits, so nothing of that size exists.  A kernel family of its
+ * own: never a fallback to or from acattn_unnorm_attention_* or acattn_calibrated_attention_*.
+ *
+ * Supported (acattn_timeaware_attention_supported: 1 / 0 from the configuration alone, no launch): everything
+ * acattn_unnorm_attention_supported requires (adversarial, GATE, two_level, STRUCTURED mask, both spatial terms, 1 <= L <= 64,
+ * head size 16 / 32 / 64, EXPLICIT or COUNTER randomness of the layer's own draws), and 1 <= time_span with
+ * 8 (time_span + 1) dh <= 160 KiB (the two gradient tables of one head in one workgroup's LDS: time_span <= 319 at head size
+ * 64, so the reference's default 256 fits every head size), 0 <= p_time < 1.  Anything else: -1 and a text naming the limit.
+ *
+ * time_index values are CLAMPED into [0, time_span] by every kernel before a table is addressed (get_time_matrix,
+ * actisasrec.py:148-157, already clips: a bad batch gives a wrong number, never an out-of-bounds access).  Nothing is read
+ * for a key j >= L of the tile padding: no index, and TK, TV, pk, pv count as zero there.  Every key j < L enters the value
+ * sums, padded and future ones included (A_attacked = N where M = 0); a zero weight of the CALIBRATED mixture skips its TV
+ * row, so a non-finite table row reached only through masked keys shows in ctx_attacked alone.
+ *
+ * Time dropout: keep_time_k / keep_time_v given = those bits; both NULL with p_time > 0 = the counter stream of
+ * (time_seed + *time_seed_device), the bits acattn_time_rng_materialize writes -- a stream disjoint from
+ * acattn_rng_materialize's, and a seed of its own because all layers of one forward share the dropped tensors
+ * (actisasrec.py:123-124 runs once per forward).  p_time = 0: no dropout. */
+typedef struct acattn_time_ext {
+  const float* pos_k;         /* [B,L,H] dropout(absolute_pos_K_embedding(position_ids))   actisasrec.py:110, :121 */
+  const float* pos_v;         /* [B,L,H] dropout(absolute_pos_V_embedding(position_ids))   actisasrec.py:111, :122 */
+  const int32_t* time_index;  /* [B,L,L] get_time_matrix(time_seq)                          actisasrec.py:148-157 */
+  const float* time_k;        /* [time_span + 1, H] time_matrix_emb_K_embedding.weight      actisasrec.py:56 */
+  const float* time_v;        /* [time_span + 1, H] time_matrix_emb_V_embedding.weight      actisasrec.py:57 */
+  int32_t time_span;
+  float p_time;               /* hidden_dropout_prob of actisasrec.py:123-124; 0 = none */
+  const uint8_t* keep_time_k; /* [B,L,L,H] 0/1 or NULL */
+  const uint8_t* keep_time_v; /* [B,L,L,H] 0/1 or NULL */
+  uint64_t time_seed;
+  const uint64_t* time_seed_device; /* optional, added to time_seed when a kernel starts */
+} acattn_time_ext;
+
+/* What the backward writes beyond acattn_bwd_io (all required, fully overwritten).  d pos_v = dv and is not written again.
+ * d_time_k / d_time_v are the TRUE derivatives, row 0 included (nn.Embedding(padding_idx=0) zeroes that row: the caller's
+ * business).  They come from a second launch (timeaware_table_grad_kernel) that sums in LDS and flushes with float atomics:
+ * these two outputs alone may differ in the last bits between two launches; every other output keeps the un-normalised
+ * core's property (no atomic, same bits). */
+typedef struct acattn_time_grads {
+  float* d_pos_k;  /* [B,L,H]: sum_i dS_ij q_i, the product share of dk (the spatial affines' share goes to dk alone) */
+  float* d_time_k; /* [time_span + 1, H] */
+  float* d_time_v; /* [time_span + 1, H] */
+  void* workspace; /* 3 * B * n_heads * L * L floats (contents irrelevant): dS, A_attacked, A_calibrated for the second launch */
+} acattn_time_grads;
+
+int acattn_timeaware_attention_supported(const acattn_problem* p, const acattn_time_ext* t);
+/* Replaces transformer_layers.py:1107-1180 (cal_origin_qkv after the projections), :1065-1082, :1296-1303 and the three
+ * matmuls of :1087-1090.  Outputs as acattn_unnorm_attention_fwd (row_stats slots 0-1, penalty_part). */
+int acattn_timeaware_attention_fwd(const acattn_problem* p, const acattn_time_ext* t, const acattn_fwd_out* out, void* stream);
+/* The backward of the above: acattn_unnorm_attention_bwd's contract for `io`, with dq carrying the pk and TK terms and
+ * dA_x[i,j] = d_ctx_x[i].(v_j + pv_j + TV_ij), plus `grads`. */
+int acattn_timeaware_attention_bwd(const acattn_problem* p, const acattn_time_ext* t, const acattn_bwd_io* io,
+                                   const acattn_time_grads* grads, void* stream);
+/* The counter-mode keep bits of the two time dropouts for (seed, shape): uint8 [B,L,L,H] each (either may be NULL). */
+int acattn_time_rng_materialize(int32_t B, int32_t L, int32_t H, uint64_t seed, float p, uint8_t* keep_k, uint8_t* keep_v,
+                                void* stream);
+
 #ifdef __cplusplus
 }
 #endif
