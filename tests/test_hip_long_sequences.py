@@ -1,7 +1,9 @@
 """GPU suite (-m gpu): the long form of the calibrated attention core (csrc/acattn_long_fwd.inc, acattn_long_bwd.inc),
 208 < L <= 496 -- and at L <= 208 with the long form pinned -- through the operator, the encoder, both models and the trainer.
 
-Cases: tests/_long_cases.py (its conditioning is checked on the CPU by tests/test_long_sequence_cases_cpu.py).
+Cases: tests/_long_cases.py (its conditioning is checked on the CPU by tests/test_long_sequence_cases_cpu.py).  The forward
+oracle and the comparison of live and fully masked rows live in tests/_attention_fwd_ref.py (shared with
+tests/test_hip_fwd_edges.py).
 
 Forward bounds, on query rows the mask lets see a key: |M - ref| <= 5e-6 and both contexts <= 1e-4 against
 oracle/ac_tsr_ref.py::core_from_projected in float32 (the project's figures: tests/test_hip_onehop.py).  row_stats are the
@@ -29,13 +31,14 @@ import ac_tsr_amd as A
 from ac_tsr_amd import _lib, attn_launch, ops
 from oracle import ac_tsr_ref as O
 from tests import _attention_fp64 as F
+from tests._attention_fwd_ref import (CTX_BOUND, DEAD_CAP, M_BOUND, STAT_BOUND, check_forward as _check_forward,  # noqa: F401
+                                      ocfg as _ocfg, oracle_forward as _oracle_forward)
 from tests import _long_cases as LC
 from tests import test_hip_attention_bwd_fp64 as T64
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 SEED = 777
-M_BOUND, CTX_BOUND, STAT_BOUND, DEAD_CAP = 5e-6, 1e-4, 1e-4, 2e-3
 
 
 @pytest.fixture(autouse=True, scope="module")
@@ -55,51 +58,6 @@ def pins():
     lib.acattn_select_backward_kernel(_lib.BWD_AUTO)
 
 
-def _ocfg(c):
-    return O.EncoderCfg(n_layers=1, n_heads=c.nh, hidden_size=c.H, inner_size=4 * c.H, combine_option=c.combine,
-                        use_order="order" in c.terms, use_distance="distance" in c.terms, two_level=True, seq_length=c.L,
-                        attn_dropout_prob=c.p_drop)
-
-
-def _oracle_forward(c, pr, draws, dtype):
-    """core_from_projected in `dtype` plus the log-normalisers of its soft-maxes ([B, nh, L] each)."""
-    with F.default_dtype(dtype), torch.no_grad():
-        t = {k: v.to(dtype) for k, v in pr.t.items()}
-        cast = lambda v: None if v is None else v.to(dtype)
-        mask = pr.mask_dense.to(dtype)
-        cfg = _ocfg(c)
-        kw = {k: t[k] if (("order" in k and cfg.use_order) or (k in ("w_dist", "b_dist", "scalar") and cfg.use_distance)) else None
-              for k in ("w_order", "b_order", "w_dist", "b_dist", "scalar")}
-        ref = O.core_from_projected(t["q"], t["k"], t["v"], t["qa"], t["ka"], t["gl"] if c.combine == "gate" else None, mask,
-                                    kw["w_order"], kw["b_order"], kw["w_dist"], kw["b_dist"], kw["scalar"], cfg,
-                                    cast(draws["noise"]), keep_after=cast(draws["keep_after"]), keep_mask=cast(draws["keep_mask"]),
-                                    anneal_rate=c.anneal_rate, materialize=False)
-        heads = lambda x: O._heads(x, c.nh).permute(0, 2, 1, 3)
-        q, k = heads(t["q"]), heads(t["k"])
-        dh = c.H // c.nh
-        p = {"attack_attention.order_affine.weight": kw["w_order"], "attack_attention.order_affine.bias": kw["b_order"],
-             "attack_attention.distance_affine.weight": kw["w_dist"], "attack_attention.distance_affine.bias": kw["b_dist"],
-             "attack_attention.scalar": kw["scalar"]}
-        e_o, e_d = O.spatial_errors(q, k, p, cfg, materialize=False)
-        lse = lambda x: torch.logsumexp(x, dim=-1)
-        P, M = ref["after"], ref["M"]
-        stats = [lse((q @ k.transpose(-1, -2) + e_o + e_d) / math.sqrt(dh) + mask),
-                 lse(heads(t["qa"]) @ heads(t["ka"]).transpose(-1, -2) / math.sqrt(dh) + mask),
-                 lse(P * M + cast(draws["noise"]) * (1 - M) + mask)]
-        v_arg = P * torch.exp(1 - M) + mask
-        stats.append(lse(v_arg))
-        Ac = torch.softmax(v_arg, dim=-1)
-        if c.combine == "fixed":
-            inner = P + 0.5 * Ac
-            comb, lse_f = torch.softmax(inner, dim=-1), lse(inner)
-        else:
-            g = torch.sigmoid(t["gl"]).unsqueeze(1) if c.combine == "gate" else c.anneal_rate
-            comb, lse_f = g * P + (1 - g) * Ac, None
-        stats.append(lse(comb + mask))
-        ref["stats"], ref["lse_f"] = torch.stack(stats, dim=-1), lse_f
-    return ref
-
-
 def _device_problem(c, pr, draws, explicit=True, seed=SEED):
     """(lib, acattn_problem, the device tensors it points to) through ops._fill_problem, the operator's own checks."""
     lib = _lib.load()
@@ -117,40 +75,6 @@ def _device_problem(c, pr, draws, explicit=True, seed=SEED):
                              flat(x["w_dist"]) if "distance" in c.terms else None, x["b_dist"], x["scalar"], None, cfg, c.p_drop,
                              rnd, seed, keep)
     return lib, prob, x, keep
-
-
-def _check_forward(c, pr, got, ref32, ref64, tag=""):
-    """`got` = (ctx_attacked, ctx_calibrated, M, row_stats) as CPU tensors."""
-    ctx_a, ctx_c, M, stats = got
-    for name, t in (("ctx_attacked", ctx_a), ("ctx_calibrated", ctx_c), ("M", M), ("row_stats", stats[..., :5])):
-        assert torch.isfinite(t).all(), f"{c.id}{tag}: {name} holds an element no kernel wrote (or a non-finite value)"
-    live, dead = ~pr.dead, pr.dead  # [B, L]
-    figures = {}
-    for name, t, bound in (("M", M, M_BOUND), ("ctx_attacked", ctx_a, CTX_BOUND), ("ctx_calibrated", ctx_c, CTX_BOUND)):
-        row = live[:, None, :, None] if name == "M" else live[:, :, None]
-        e = ((t - ref32[name]).abs() * row).max().item()
-        figures[name] = e
-        assert e <= bound, f"{c.id}{tag}: {name} differs from the fp32 oracle by {e:.3e} > {bound:.0e}"
-        if dead.any():
-            drow = ~row
-            scale = (ref32[name].abs() * drow).max().item()
-            ed = ((t - ref32[name]).abs() * drow).max().item()
-            figures[name + "_dead"] = ed
-            assert ed <= DEAD_CAP * scale + F.ABS_FLOOR, f"{c.id}{tag}: fully masked rows of {name}: {ed:.3e} of {scale:.3e}"
-    es = ((stats[..., :5].double() - ref64["stats"]).abs() * live[:, None, :, None]).max().item()
-    figures["row_stats"] = es
-    assert es <= STAT_BOUND, f"{c.id}{tag}: row_stats differ from the fp64 normalisers by {es:.3e}"
-    if dead.any():
-        ed = ((stats[..., :5].double() - ref64["stats"]).abs() * dead[:, None, :, None]).max().item()
-        assert ed <= 2 * 2.0 ** -10 + STAT_BOUND, f"{c.id}{tag}: row_stats of fully masked rows: {ed:.3e}"
-    if ref64["lse_f"] is not None:
-        ef = (stats[..., 5].double() - ref64["lse_f"]).abs().max().item()
-        assert ef <= STAT_BOUND, f"{c.id}{tag}: the inner soft-max's normaliser (combine fixed): {ef:.3e}"
-    # what the fp32 oracle itself is from the fp64 one on these rows: the yardstick's own error next to the kernel's
-    e32 = {n: ((ref32[n].double() - ref64[n]).abs() * (live[:, None, :, None] if n == "M" else live[:, :, None])).max().item()
-           for n in ("M", "ctx_attacked", "ctx_calibrated")}
-    print(f"long_sequences_accuracy case={c.id}{tag} " + " ".join(f"{k}={v:.3e}" for k, v in figures.items()) +
-          " oracle32_vs_64: " + " ".join(f"{k}={v:.3e}" for k, v in e32.items()))
 
 
 # ---- 1. forward, explicit randomness --------------------------------------------------------------------------------------
