@@ -251,14 +251,9 @@ def spatial_attention_bwd_launch(lib, prob, q, d_ctx, n_heads: int, read_rows=No
     return dq, dk, dv, part
 
 
-def unnorm_attention_supported(lib, prob) -> bool:
-    """acattn_unnorm_attention_supported: does the un-normalised pair (csrc/acattn_unnorm.hip) cover this configuration?"""
-    return bool(lib.acattn_unnorm_attention_supported(C.byref(prob)))
-
-
-def unnorm_attention_fwd_launch(lib, prob, q, n_heads: int, *, want_penalty: bool, poison: bool = False):
-    """One acattn_unnorm_attention_fwd call for a filled `prob` (ACSSEPT's core: no re-normalisation of the mixtures).
-    Returns (ctx_attacked, ctx_calibrated, M, row_stats, penalty_part or None)."""
+def _l64_fwd_out(q, n_heads: int, want_penalty: bool, poison: bool):
+    """The forward outputs of the two L <= 64 cores without re-normalisation: (FwdOut, (ctx_attacked, ctx_calibrated, M,
+    row_stats, penalty_part or None))."""
     B, L, H = q.shape
     new = allocator(q, poison or POISON)
     out = _lib.FwdOut()
@@ -268,17 +263,13 @@ def unnorm_attention_fwd_launch(lib, prob, q, n_heads: int, *, want_penalty: boo
     if want_penalty:
         pen = new(B, n_heads, (L + 15) // 16)
         out.penalty_part = _ptr(pen)
-    _lib.check(lib.acattn_unnorm_attention_fwd(C.byref(prob), C.byref(out), _stream()), "unnorm_attention_fwd")
-    return ctx_att, ctx_cal, M, stats, pen
+    return out, (ctx_att, ctx_cal, M, stats, pen)
 
 
-def unnorm_attention_bwd_launch(lib, prob, q, n_heads: int, M, stats, *, d_att=None, d_cal=None, d_M=None, d_pen=None,
-                                read_rows=None, attack_only: bool = False, poison: bool = False):
-    """One acattn_unnorm_attention_bwd call: allocates the gradients and the parameter partials.  Returns (dq, dk, dv, dqa,
-    dka, dgate_part [B,n_heads,L,L], part) -- attention_bwd_launch's tuple.  `read_rows` / `attack_only` travel as the hints
-    they are; the kernel writes every output whatever they say."""
+def _l64_bwd_io(new, q, n_heads: int, M, stats, d_att, d_cal, d_M, d_pen):
+    """The backward's BwdIO of the same two cores with the gradients, the parameter partials and the per-head gate partials
+    allocated by `new`: (BwdIO, (dq, dk, dv, dqa, dka, dgate_part [B,n_heads,L,L], part))."""
     B, L, H = q.shape
-    new = allocator(q, poison or POISON)
     io = _lib.BwdIO()
     io.attack_mask, io.row_stats = _ptr(M), _ptr(stats)
     io.d_ctx_attacked, io.d_ctx_calibrated, io.d_attack_mask = _ptr(d_att), _ptr(d_cal), _ptr(d_M)
@@ -286,13 +277,35 @@ def unnorm_attention_bwd_launch(lib, prob, q, n_heads: int, M, stats, *, d_att=N
     dq, dk, dv, dqa, dka = (new(B, L, H) for _ in range(5))
     io.dq, io.dk, io.dv, io.dqa, io.dka = _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dqa), _ptr(dka)
     part = partials(io, q, n_heads, new)
+    dgate_part = new(B, n_heads, L, L)
+    io.dgate_logits = _ptr(dgate_part)
+    return io, (dq, dk, dv, dqa, dka, dgate_part, part)
+
+
+def unnorm_attention_supported(lib, prob) -> bool:
+    """acattn_unnorm_attention_supported: does the un-normalised pair (csrc/acattn_unnorm.hip) cover this configuration?"""
+    return bool(lib.acattn_unnorm_attention_supported(C.byref(prob)))
+
+
+def unnorm_attention_fwd_launch(lib, prob, q, n_heads: int, *, want_penalty: bool, poison: bool = False):
+    """One acattn_unnorm_attention_fwd call for a filled `prob` (ACSSEPT's core: no re-normalisation of the mixtures).
+    Returns (ctx_attacked, ctx_calibrated, M, row_stats, penalty_part or None)."""
+    out, res = _l64_fwd_out(q, n_heads, want_penalty, poison)
+    _lib.check(lib.acattn_unnorm_attention_fwd(C.byref(prob), C.byref(out), _stream()), "unnorm_attention_fwd")
+    return res
+
+
+def unnorm_attention_bwd_launch(lib, prob, q, n_heads: int, M, stats, *, d_att=None, d_cal=None, d_M=None, d_pen=None,
+                                read_rows=None, attack_only: bool = False, poison: bool = False):
+    """One acattn_unnorm_attention_bwd call: allocates the gradients and the parameter partials.  Returns (dq, dk, dv, dqa,
+    dka, dgate_part [B,n_heads,L,L], part) -- attention_bwd_launch's tuple.  `read_rows` / `attack_only` travel as the hints
+    they are; the kernel writes every output whatever they say."""
+    io, res = _l64_bwd_io(allocator(q, poison or POISON), q, n_heads, M, stats, d_att, d_cal, d_M, d_pen)
     if read_rows is not None:
         io.read_rows, io.n_read_rows = _ptr(read_rows), read_rows.shape[1]
     io.attack_only = int(attack_only)
-    dgate_part = new(B, n_heads, L, L)
-    io.dgate_logits = _ptr(dgate_part)
     _lib.check(lib.acattn_unnorm_attention_bwd(C.byref(prob), C.byref(io), _stream()), "unnorm_attention_bwd")
-    return dq, dk, dv, dqa, dka, dgate_part, part
+    return res
 
 
 def fill_time_ext(pos_k, pos_v, time_index, time_k, time_v, p_time: float, *, keep_k=None, keep_v=None, seed: int = 0,
@@ -317,18 +330,10 @@ def timeaware_attention_supported(lib, prob, text) -> bool:
 def timeaware_attention_fwd_launch(lib, prob, text, q, n_heads: int, *, want_penalty: bool, poison: bool = False):
     """One acattn_timeaware_attention_fwd call (ACTiSASRec's core).  Returns (ctx_attacked, ctx_calibrated, M, row_stats,
     penalty_part or None)."""
-    B, L, H = q.shape
-    new = allocator(q, poison or POISON)
-    out = _lib.FwdOut()
-    ctx_att, ctx_cal, M, stats = new(B, L, H), new(B, L, H), new(B, n_heads, L, L), new(B, n_heads, L, _lib.NSTAT)
-    out.ctx_attacked, out.ctx_calibrated, out.attack_mask, out.row_stats = _ptr(ctx_att), _ptr(ctx_cal), _ptr(M), _ptr(stats)
-    pen = None
-    if want_penalty:
-        pen = new(B, n_heads, (L + 15) // 16)
-        out.penalty_part = _ptr(pen)
+    out, res = _l64_fwd_out(q, n_heads, want_penalty, poison)
     _lib.check(lib.acattn_timeaware_attention_fwd(C.byref(prob), C.byref(text), C.byref(out), _stream()),
                "timeaware_attention_fwd")
-    return ctx_att, ctx_cal, M, stats, pen
+    return res
 
 
 def timeaware_attention_bwd_launch(lib, prob, text, q, n_heads: int, M, stats, n_table_rows: int, *, d_att=None, d_cal=None,
@@ -338,19 +343,11 @@ def timeaware_attention_bwd_launch(lib, prob, text, q, n_heads: int, M, stats, n
     The table gradients are the kernel's true derivatives, row 0 included."""
     B, L, H = q.shape
     new = allocator(q, poison or POISON)
-    io = _lib.BwdIO()
-    io.attack_mask, io.row_stats = _ptr(M), _ptr(stats)
-    io.d_ctx_attacked, io.d_ctx_calibrated, io.d_attack_mask = _ptr(d_att), _ptr(d_cal), _ptr(d_M)
-    io.d_penalty_part = _ptr(d_pen)
-    dq, dk, dv, dqa, dka = (new(B, L, H) for _ in range(5))
-    io.dq, io.dk, io.dv, io.dqa, io.dka = _ptr(dq), _ptr(dk), _ptr(dv), _ptr(dqa), _ptr(dka)
-    part = partials(io, q, n_heads, new)
-    dgate_part = new(B, n_heads, L, L)
-    io.dgate_logits = _ptr(dgate_part)
+    io, res = _l64_bwd_io(new, q, n_heads, M, stats, d_att, d_cal, d_M, d_pen)
     g = _lib.TimeGrads()
     d_pos_k, d_time_k, d_time_v = new(B, L, H), new(n_table_rows, H), new(n_table_rows, H)
     ws = new(3, B, n_heads, L, L)
     g.d_pos_k, g.d_time_k, g.d_time_v, g.workspace = _ptr(d_pos_k), _ptr(d_time_k), _ptr(d_time_v), _ptr(ws)
     _lib.check(lib.acattn_timeaware_attention_bwd(C.byref(prob), C.byref(text), C.byref(io), C.byref(g), _stream()),
                "timeaware_attention_bwd")
-    return dq, dk, dv, dqa, dka, dgate_part, part, d_pos_k, d_time_k, d_time_v
+    return res + (d_pos_k, d_time_k, d_time_v)

@@ -1,7 +1,7 @@
 // The TIME-INTERVAL attention core of ACTiSASRec (L <= 64): recbole/model/transformer_layers.py:1010-1422, the encoder
 // actisasrec.py:59 builds.  A sibling of acattn_unnorm.hip (same frame, same mixtures, none of the three re-normalising
-// soft-maxes), not a flag through it: nothing of that file is called here.  Per head, with pk_j / pv_j the head's slices of the
-// dropped absolute-position rows, t_ij = time_index[b, i, j], TK_ij = drop(time_k[t_ij]), TV_ij = drop(time_v[t_ij]):
+// soft-maxes), not a flag through it: the frame both share is acattn_row64.h, the time terms are here.  Per head, with
+// pk_j / pv_j the head's slices of the dropped absolute-position rows, t_ij = time_index[b, i, j], TK_ij = drop(time_k[t_ij]), TV_ij = drop(time_v[t_ij]):
 //     S  = q.(K + pk)^T + q_i.TK_ij + e_order + e_distance       transformer_layers.py:1125-1166 (the spatial terms see the
 //                                                                plain k only, :1142-1145)
 //     P  = dropout(softmax(S / sqrt(dh) + mask))                 :1168-1176
@@ -28,18 +28,15 @@
 // real batches put most pairs on row time_span and row 0), and flushes once with one float atomic per non-zero element.
 // Those two outputs alone depend on the order of atomics; everything else gives the same bits in two launches.
 #include <algorithm>
-#include <type_traits>
 
-#include "acattn_common.h"
+#include "acattn_row64.h"
+
+#define ACATTN_L64_WHAT "time-aware attention"
+#include "acattn_l64_checks.inc"
 
 namespace {
 
-constexpr float kLog2e = 1.44269504088896340736f;
-constexpr float kLn2 = 0.69314718055994530942f;
 constexpr int kMaxLds = 160 * 1024;
-
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float hsum(const f4 v) { return (v[0] + v[1]) + (v[2] + v[3]); }
 
 // ------------------------------------------------------------------------------------------------------------------------
 // the time dropout's counter stream: one 32-bit word per (pair = (b L + i) L + j, table, 32 columns).  p == 0.5: column c
@@ -123,24 +120,6 @@ struct TimeCtx {
   }
 };
 
-// What a workgroup stages once: K + pk, Ka, V + pv rows of its head ([LP][DH + 4], rows past L zeros) and per key the halves
-// of the two spatial affines (from the plain k), log(distance + 1) and the key's validity.
-template <int DH>
-struct Staged {
-  static constexpr int VS = DH + 4;
-  float *Ks, *Kas, *Vs, *s_co, *s_cd, *s_lt, *s_ok;
-  __device__ __forceinline__ Staged(float* base, int LP) {
-    Ks = base;
-    Kas = Ks + LP * VS;
-    Vs = Kas + LP * VS;
-    s_co = Vs + LP * VS;
-    s_cd = s_co + LP;
-    s_lt = s_cd + LP;
-    s_ok = s_lt + LP;
-  }
-  static constexpr int floats(int LP) { return 3 * LP * VS + 4 * LP; }
-};
-
 // blockDim.x == 4 * LP: thread idx + it * blockDim covers the LP x DH/4 16-byte pieces of a matrix in DH / 16 rounds
 template <int DH>
 __device__ __forceinline__ void stage(const acattn_problem& P, const acattn_time_ext& T, const Staged<DH>& S, size_t rowbase,
@@ -183,159 +162,19 @@ __device__ __forceinline__ void stage(const acattn_problem& P, const acattn_time
   }
 }
 
-// One lane's view of its query row: lane = 16 g + c holds, of query row i = 16 qb + c, the keys 16 t + 4 g + r of tile t.
-// Of the row's dh-vectors (q, qa, the context cotangents, the time rows) it holds the columns KS g .. KS g + KS - 1.
+// RowCore plus the time terms.  Of the context cotangents and the time rows the lane holds the columns KS g .. KS g + KS - 1,
+// as it does of q and qa.
 template <int DH>
-struct Row {
-  static constexpr int KS = DH / 4, VS = DH + 4;
-  const acattn_problem& P;
-  const Staged<DH>& S;
+struct Row : RowCore<DH> {
+  using Core = RowCore<DH>;
+  using Core::KS, Core::VS, Core::P, Core::L, Core::c, Core::g, Core::i, Core::row_ok, Core::rowbase, Core::hoff, Core::qf;
+  using Core::ll_row;  // this row's L indices of time_index
   const TimeCtx& TC;
-  int L, c, g, qb, i;
-  bool row_ok, dead, causal, has_drop;
-  size_t rowbase, bh, prow, trow;
-  int hoff;
-  float ao2, ad, sc, scale2, keep_scale;
-  RngKey rkey;
-  float qf[KS], qaf[KS];
 
   __device__ __forceinline__ Row(const acattn_problem& P_, const Staged<DH>& S_, const TimeCtx& TC_, int b, int h, int qb_,
                                  int lane)
-      : P(P_), S(S_), TC(TC_) {
-    L = P.L;
-    c = lane & 15;
-    g = lane >> 4;
-    qb = qb_;
-    i = 16 * qb + c;
-    row_ok = i < L;
-    causal = P.causal != 0;
-    rowbase = (size_t)b * L;
-    hoff = h * DH;
-    bh = (size_t)b * P.n_heads + h;
-    prow = (bh * L + (row_ok ? i : 0)) * (size_t)L;
-    trow = (rowbase + (row_ok ? i : 0)) * (size_t)L;  // this row's L indices of time_index (a row past L reads row 0's)
-    has_drop = P.p_drop > 0.f;
-    keep_scale = has_drop ? 1.0f / (1.0f - P.p_drop) : 1.0f;
-    scale2 = kLog2e / sqrtf((float)DH);
-    // a row none of whose keys is allowed: the mask's common shift is dropped, the soft-max runs over all L keys
-    const unsigned long long valid = __ballot(lane < L && S.s_ok[lane < L ? lane : 0] != 0.f);
-    const unsigned long long upto = (causal && i < 63) ? ((2ull << i) - 1ull) : ~0ull;
-    dead = !row_ok || (valid & upto) == 0ull;
-    const size_t off = (rowbase + (row_ok ? i : 0)) * P.H + hoff + KS * g;
-    float ao = 0.f, adq = 0.f;
-#pragma unroll
-    for (int s4 = 0; s4 < KS / 4; ++s4) {
-      f4 tq = {0.f, 0.f, 0.f, 0.f}, ta = tq;
-      if (row_ok) {
-        tq = *(const f4*)(P.q + off + 4 * s4);
-        ta = *(const f4*)(P.qa + off + 4 * s4);
-      }
-      const f4 a = *(const f4*)(P.w_order + KS * g + 4 * s4), d = *(const f4*)(P.w_dist + KS * g + 4 * s4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        qf[4 * s4 + e] = tq[e];
-        qaf[4 * s4 + e] = ta[e];
-        ao += tq[e] * a[e];
-        adq += tq[e] * d[e];
-      }
-    }
-    ao2 = -kLog2e * (quad_sum(ao) + P.b_order[0]);
-    ad = quad_sum(adq) + P.b_dist[0];
-    sc = P.scalar[0];
-    rkey = rng_key(P.seed + (P.seed_device ? *P.seed_device : 0ull));
-  }
+      : Core(P_, S_, b, h, qb_, lane, true), TC(TC_) {}
 
-  // additive mask of tile t in exp2 units: 0 allowed, -10000 log2(e) masked, -inf in the tile padding
-  __device__ __forceinline__ f4 mask4(int t) const {
-    const f4 ok4 = *(const f4*)(S.s_ok + 16 * t + 4 * g);
-    f4 m;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int j = 16 * t + 4 * g + r;
-      const bool allowed = dead || (ok4[r] != 0.f && (!causal || j <= i));
-      m[r] = j >= L ? ACATTN_NEG_INF : (allowed ? 0.f : ACATTN_MASK_FILL * kLog2e);
-    }
-    return m;
-  }
-  // pr = sigmoid(order affine), val = the probability the order term takes the log of (pr for a key after the query,
-  // 1 - pr otherwise; transformer_layers.py:1152-1156), df = log(|i - j| + 1) - distance affine (:1158-1164)
-  __device__ __forceinline__ void spatial(int t, f4& pr, f4& val, f4& df) const {
-    const f4 ea = *(const f4*)(S.s_co + 16 * t + 4 * g) + ao2;
-    const f4 cd4 = *(const f4*)(S.s_cd + 16 * t + 4 * g);
-    const int d0 = i - (16 * t + 4 * g);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      pr[r] = fast_rcp(1.0f + ex2(ea[r]));
-      val[r] = (d0 - r < 0) ? pr[r] : 1.0f - pr[r];
-      const int dist = d0 - r < 0 ? r - d0 : d0 - r;
-      df[r] = S.s_lt[dist] - (cd4[r] + ad);  // (dist < LP: both indices are)
-    }
-  }
-  // 4 keys of this row from the row's L floats (NULL = zeros); zeros past L and for rows past L
-  __device__ __forceinline__ f4 load_row(const float* rowp, int t) const {
-    const int j0 = 16 * t + 4 * g;
-    f4 v = {0.f, 0.f, 0.f, 0.f};
-    if (rowp && row_ok && j0 < L) {
-      const float* p = rowp + j0;
-      if (j0 + 3 < L) {
-        v = *(const f4u*)p;
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (j0 + r < L) v[r] = p[r];
-      }
-    }
-    return v;
-  }
-  // the same from a [B,nh,L,L] tensor
-  __device__ __forceinline__ f4 load_seg(const float* t4, int t) const { return load_row(t4 ? t4 + prow : nullptr, t); }
-  __device__ __forceinline__ const float* gate_row() const { return P.gate_logits + (rowbase + (row_ok ? i : 0)) * L; }
-  __device__ __forceinline__ void store_seg(float* t4, int t, const f4 v) const {
-    const int j0 = 16 * t + 4 * g;
-    if (row_ok && j0 < L) {
-      float* p = t4 + prow + j0;
-      if (j0 + 3 < L) {
-        *(f4u*)p = v;
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (j0 + r < L) p[r] = v[r];
-      }
-    }
-  }
-  __device__ __forceinline__ uint32_t load_bits(const uint8_t* k4, int t) const {
-    uint32_t bits = 0xFu;
-    if (k4 && row_ok) {
-      bits = 0;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int j = 16 * t + 4 * g + r;
-        bits |= ((j < L ? k4[prow + j] : (uint8_t)1) ? 1u : 0u) << r;
-      }
-    }
-    return bits;
-  }
-  // the draws of tile t: four normals (zero past L) and the keep bits of P's and M's dropout
-  __device__ __forceinline__ void draws(int t, f4& n, uint32_t& ka, uint32_t& km) const {
-    ka = km = 0xFu;
-    if (P.rng_mode == ACATTN_RNG_COUNTER) {
-      const RngGroup rg = rng_group(rkey, (uint32_t)(bh * L + i), (uint32_t)(4 * t + g), P.p_drop);
-      n = rg.n;
-      if (has_drop) {
-        ka = rg.keep_after;
-        km = rg.keep_mask;
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (16 * t + 4 * g + r >= L) n[r] = 0.f;
-    } else {
-      n = load_seg(P.noise, t);
-      if (has_drop) {
-        ka = load_bits(P.keep_after, t);
-        km = load_bits(P.keep_mask, t);
-      }
-    }
-  }
   // The value the lane that owns key (t, gj, r) of this row holds, in all four lanes of the row (exact: x + 0 + 0 + 0).
   __device__ __forceinline__ float from_owner(float mine, int gj) const { return quad_sum(g == gj ? mine : 0.f); }
 
@@ -350,7 +189,7 @@ struct Row {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int j = 16 * t + 4 * gj + r;
-          if (j < L) f(t, gj, r, j, trow + j);  // (wave-uniform)
+          if (j < L) f(t, gj, r, j, ll_row + j);  // (wave-uniform)
         }
   }
   // acc[t][r] += v[.] . drop(table[t_ij])[.] over the head's columns, for every key of the row; `v0`, `v1`: the lane's KS
@@ -407,50 +246,9 @@ struct Row {
   // x = S / sqrt(dh) + mask and y = qa.Ka^T / sqrt(dh) + mask, both in exp2 units
   template <int NTB>
   __device__ __forceinline__ void scores(f4 (&x)[NTB], f4 (&y)[NTB]) const {
-    const float nhs2 = -0.5f * (sc * sc);
-#pragma unroll
-    for (int t = 0; t < NTB; ++t) {
-      f4 pr, val, df, lg;
-      spatial(t, pr, val, df);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) lg[r] = __builtin_amdgcn_logf(val[r] + ACATTN_LOG_EPS);
-      x[t] = lg * kLn2 + (df * df) * nhs2;
-      y[t] = f4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int s4 = 0; s4 < KS / 4; ++s4) {
-#pragma unroll
-      for (int t = 0; t < NTB; ++t) {
-        const f4 k4 = *(const f4*)(S.Ks + (16 * t + c) * VS + KS * g + 4 * s4);
-        const f4 a4 = *(const f4*)(S.Kas + (16 * t + c) * VS + KS * g + 4 * s4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          x[t] = mfma16(k4[e], qf[4 * s4 + e], x[t]);
-          y[t] = mfma16(a4[e], qaf[4 * s4 + e], y[t]);
-        }
-      }
-    }
+    this->template scores_dense<NTB>(x, y);
     time_dots<NTB, false>(0, qf, qf, x, x);  // + q_i . TK_ij
-#pragma unroll
-    for (int t = 0; t < NTB; ++t) {
-      const f4 mk = mask4(t);
-      x[t] = x[t] * scale2 + mk;
-      y[t] = y[t] * scale2 + mk;
-    }
-  }
-  // out[query c][16 dt + 4 g + r] = sum over the keys of w[query c][key] X[key][.], X one of the staged matrices
-  template <int NTB>
-  __device__ __forceinline__ void times_keys(const float* X, const f4 (&w)[NTB], f4 (&o)[DH / 16]) const {
-#pragma unroll
-    for (int dt = 0; dt < DH / 16; ++dt) o[dt] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < NTB; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float* xp = X + (16 * t + 4 * g + r) * VS + c;
-#pragma unroll
-        for (int dt = 0; dt < DH / 16; ++dt) o[dt] = mfma16(xp[16 * dt], w[t][r], o[dt]);
-      }
+    this->template scores_finish<NTB>(x, y);
   }
   // the lane's KS columns of the row of a [B,L,H] tensor (NULL = zeros)
   __device__ __forceinline__ void load_cols(const float* d, float (&v)[KS]) const {
@@ -491,7 +289,6 @@ struct Row {
 #pragma unroll
     for (int dt = 0; dt < DH / 16; ++dt) o[dt] += *(const f4*)(tr + c * VS + 16 * dt + 4 * g);
   }
-  __device__ __forceinline__ f4 live(const f4 v) const { return row_ok ? v : f4{0.f, 0.f, 0.f, 0.f}; }
 };
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -609,15 +406,6 @@ struct BwdShared {
   }
   static constexpr int floats(int LP, int DH) { return 4 * LP * (LP + 4) + 8 * LP + 2 * LP + 3 * LP + LP * (DH + 4); }
 };
-
-// sum over the 16 query rows of a block (lanes of equal g), for every lane
-__device__ __forceinline__ float rows16_sum(float v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  v += __shfl_xor(v, 8);
-  return v;
-}
 
 template <int DH, int NTB>
 __device__ __forceinline__ void bwd_block(const acattn_problem& P, const acattn_bwd_io& IO, const acattn_time_grads& G,
@@ -940,36 +728,20 @@ __global__ void __launch_bounds__(256) time_rng_kernel(int H, long long n, uint6
   if (keep_v) keep_v[idx] = (uint8_t)(p > 0.f ? time_keep1(time_word(key, (uint32_t)pair, 1u, (uint32_t)(col >> 5), nchunk), col, p) : 1u);
 }
 
-// The configuration this family covers (include/acattn.h); `why` receives the limit a problem breaks.
-bool timeaware_supported(const acattn_problem& p, const acattn_time_ext& t, const char** why) {
-  const char* w = nullptr;
-  if (p.B < 1 || p.L < 1 || p.H < 1 || p.n_heads < 1 || p.H % p.n_heads != 0) w = "time-aware attention: B, L, H, n_heads must be positive and H a multiple of n_heads";
-  else if (p.L > 64) w = "time-aware attention: sequence length L must be <= 64";
-  else if (p.H / p.n_heads != 16 && p.H / p.n_heads != 32 && p.H / p.n_heads != 64) w = "time-aware attention: head size must be 16, 32 or 64";
-  else if (!p.adversarial) w = "time-aware attention: needs the adversarial calibrator (adversarial = 1)";
-  else if (p.combine_option != ACATTN_COMBINE_GATE) w = "time-aware attention: combine_option must be gate (fixed / annealing are not built)";
-  else if (!p.two_level) w = "time-aware attention: two_level must be 1 (the one-level form is not built)";
-  else if (p.mask_mode != ACATTN_MASK_STRUCTURED) w = "time-aware attention: the mask must be structured (key_valid + causal); dense masks are not built";
-  else if (p.rng_mode != ACATTN_RNG_EXPLICIT && p.rng_mode != ACATTN_RNG_COUNTER) w = "time-aware attention: unknown rng_mode";
-  else if (!(p.p_drop >= 0.f && p.p_drop < 1.f)) w = "time-aware attention: p_drop must lie in [0, 1)";
-  else if (t.time_span < 1) w = "time-aware attention: time_span must be >= 1";
-  else if (8LL * ((int64_t)t.time_span + 1) * (p.H / p.n_heads) > kMaxLds) w = "time-aware attention: time_span too large: 8 (time_span + 1) head_size must be <= 160 KiB (the table gradients' LDS)";
-  else if (!(t.p_time >= 0.f && t.p_time < 1.f)) w = "time-aware attention: p_time must lie in [0, 1)";
-  else if ((int64_t)p.B * p.n_heads * p.L * p.L >= (1LL << 31) || (int64_t)p.B * p.L * p.H >= (1LL << 31)) w = "time-aware attention: tensors of 2^31 elements or more";
-  else if ((int64_t)p.B * p.L * p.L * 2 * ((p.H + 31) / 32) >= (1LL << 32)) w = "time-aware attention: B L L H / 16 must stay below 2^32 (the time dropout's counter)";
-  if (why) *why = w;
-  return w == nullptr;
+// The configuration this family covers (include/acattn.h): the limit a problem breaks, or NULL.
+const char* timeaware_limit(const acattn_problem& p, const acattn_time_ext& t) {
+  const char* w = l64_config(p);
+  if (w) return w;
+  if (t.time_span < 1) return "time-aware attention: time_span must be >= 1";
+  if (8LL * ((int64_t)t.time_span + 1) * (p.H / p.n_heads) > kMaxLds) return "time-aware attention: time_span too large: 8 (time_span + 1) head_size must be <= 160 KiB (the table gradients' LDS)";
+  if (!(t.p_time >= 0.f && t.p_time < 1.f)) return "time-aware attention: p_time must lie in [0, 1)";
+  if ((w = l64_sizes(p))) return w;
+  if ((int64_t)p.B * p.L * p.L * 2 * ((p.H + 31) / 32) >= (1LL << 32)) return "time-aware attention: B L L H / 16 must stay below 2^32 (the time dropout's counter)";
+  return nullptr;
 }
 
 const char* timeaware_pointers(const acattn_problem& p, const acattn_time_ext& t) {
-  if (!p.q || !p.k || !p.v || !p.qa || !p.ka) return "time-aware attention: q, k, v, qa, ka must be non-NULL";
-  if (!p.gate_logits) return "time-aware attention: combine_option gate needs gate_logits";
-  if (!p.key_valid) return "time-aware attention: structured mask needs key_valid";
-  if (!p.w_order || !p.b_order || !p.w_dist || !p.b_dist || !p.scalar) return "time-aware attention: both spatial terms must be present (order and distance affines, scalar)";
-  if (p.rng_mode == ACATTN_RNG_EXPLICIT) {
-    if (!p.noise) return "time-aware attention: explicit rng mode needs noise";
-    if (p.p_drop > 0.f && (!p.keep_after || !p.keep_mask)) return "time-aware attention: explicit dropout needs keep_after and keep_mask";
-  }
+  if (const char* w = l64_pointers(p)) return w;
   if (!t.pos_k || !t.pos_v || !t.time_index || !t.time_k || !t.time_v) return "time-aware attention: pos_k, pos_v, time_index, time_k, time_v must be non-NULL";
   if ((t.keep_time_k == nullptr) != (t.keep_time_v == nullptr)) return "time-aware attention: keep_time_k and keep_time_v must be given together";
   return nullptr;
@@ -980,34 +752,20 @@ size_t fwd_lds(int LP) { return sizeof(float) * (Staged<DH>::floats(LP) + LP * (
 template <int DH>
 size_t bwd_lds(int LP) { return sizeof(float) * (Staged<DH>::floats(LP) + BwdShared::floats(LP, DH)); }
 
-template <class K, class... A>
-int launch(K kern, size_t lds, int grid, int threads, hipStream_t stream, const A&... args) {
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, stream, args...);
-  return (int)hipGetLastError();
-}
-
 }  // namespace
 
 int acattn_timeaware_supported(const acattn_problem& p, const acattn_time_ext& t, const char** why) {
-  return timeaware_supported(p, t, why) ? 1 : 0;
+  const char* w = timeaware_limit(p, t);
+  if (why) *why = w;
+  return w ? 0 : 1;
 }
 
 int acattn_launch_timeaware_fwd(const acattn_problem& p, const acattn_time_ext& t, const acattn_fwd_out& o, hipStream_t stream) {
-  const char* why = nullptr;
-  if (!timeaware_supported(p, t, &why) || (why = timeaware_pointers(p, t))) {
+  const char* why = timeaware_limit(p, t);
+  if (!why) why = timeaware_pointers(p, t);
+  if (!why) why = l64_fwd_out(o);
+  if (why) {
     acattn_set_error(why);
-    return -1;
-  }
-  if (!o.ctx_attacked || !o.ctx_calibrated || !o.attack_mask) {
-    acattn_set_error("time-aware attention forward: ctx_attacked, ctx_calibrated and attack_mask must be non-NULL");
-    return -1;
-  }
-  if (o.after_spatial || o.before_spatial || o.perturbed_attention || o.calibrated_attention) {
-    acattn_set_error("time-aware attention forward: the probability dumps are not built");
     return -1;
   }
   const int nT = (p.L + 15) / 16, LP = 16 * nT, grid = p.B * p.n_heads;
@@ -1020,19 +778,10 @@ int acattn_launch_timeaware_fwd(const acattn_problem& p, const acattn_time_ext& 
 
 int acattn_launch_timeaware_bwd(const acattn_problem& p, const acattn_time_ext& t, const acattn_bwd_io& io,
                                 const acattn_time_grads& g, hipStream_t stream) {
-  const char* why = nullptr;
-  if (!timeaware_supported(p, t, &why) || (why = timeaware_pointers(p, t))) {
-    acattn_set_error(why);
-    return -1;
-  }
-  if (!io.row_stats || !io.attack_mask) why = "time-aware attention backward: needs the forward's attack_mask and row_stats";
-  else if (!io.dq || !io.dk || !io.dv || !io.dqa || !io.dka) why = "time-aware attention backward: dq, dk, dv, dqa, dka must be non-NULL";
-  else if (!io.dgate_logits) why = "time-aware attention backward: gate combine needs dgate_logits";
-  else if (!io.dw_order_part || !io.dw_dist_part || !io.dsmall_part) why = "time-aware attention backward: parameter partial buffers must be non-NULL";
-  else if (io.part_stride != 0 && io.part_stride < 2 * (p.H / p.n_heads)) why = "time-aware attention backward: part_stride is smaller than a partial row";
-  else if (io.dgate_summed) why = "time-aware attention backward: dgate_summed is not built (per-head partials only)";
-  else if (io.dqa2 || io.dka2 || io.d_ctx_calibrated2 || io.d_penalty_part2) why = "time-aware attention backward: the second cotangent set is not built";
-  else if (!g.d_pos_k || !g.d_time_k || !g.d_time_v || !g.workspace) why = "time-aware attention backward: d_pos_k, d_time_k, d_time_v and workspace must be non-NULL";
+  const char* why = timeaware_limit(p, t);
+  if (!why) why = timeaware_pointers(p, t);
+  if (!why) why = l64_bwd_io(p, io);
+  if (!why && (!g.d_pos_k || !g.d_time_k || !g.d_time_v || !g.workspace)) why = "time-aware attention backward: d_pos_k, d_time_k, d_time_v and workspace must be non-NULL";
   if (why) {
     acattn_set_error(why);
     return -1;

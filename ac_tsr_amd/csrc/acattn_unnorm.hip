@@ -20,41 +20,18 @@
 //     the reference; the common shift is dropped and the soft-max runs over all L keys (the float64 value of such a row;
 //     the reference's fp32 rounding of `score - 10000` is not reproduced).
 //
-// Frame: one workgroup per (sequence, head), one wave per 16-row query block, K, Ka, V and the key halves of the spatial
-// affines staged once in LDS, fp32 MFMA 16x16x4, exponentials in the exp2 domain, the block body compiled per tile count.
+// Frame (acattn_row64.h, shared with acattn_timeaware.hip): one workgroup per (sequence, head), one wave per 16-row query
+// block, K, Ka, V and the key halves of the spatial affines staged once in LDS, fp32 MFMA 16x16x4, exponentials in the exp2 domain, the block body compiled per tile count.
 // Backward: phase A, a wave works its query block down to dS, dSa (dq, dqa and the gate gradient leave here) and parks
 // dS, dSa, A_att, A_w as [query][key] matrices in LDS; one barrier; phase B, wave w owns key tile w and sums the query
 // blocks' contributions to dk, dka, dv in ascending block order on the MFMA.  No atomic, no exchange whose order depends
 // on timing: two launches give the same bits.
-#include <type_traits>
+#include "acattn_row64.h"
 
-#include "acattn_common.h"
+#define ACATTN_L64_WHAT "un-normalised attention"
+#include "acattn_l64_checks.inc"
 
 namespace {
-
-constexpr float kLog2e = 1.44269504088896340736f;
-constexpr float kLn2 = 0.69314718055994530942f;
-
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float hsum(const f4 v) { return (v[0] + v[1]) + (v[2] + v[3]); }
-
-// What a workgroup stages once: K, Ka, V rows of its head ([LP][DH + 4], rows past L zeros) and per key the halves of the
-// two spatial affines, log(distance + 1) and the key's validity.
-template <int DH>
-struct Staged {
-  static constexpr int VS = DH + 4;
-  float *Ks, *Kas, *Vs, *s_co, *s_cd, *s_lt, *s_ok;
-  __device__ __forceinline__ Staged(float* base, int LP) {
-    Ks = base;
-    Kas = Ks + LP * VS;
-    Vs = Kas + LP * VS;
-    s_co = Vs + LP * VS;
-    s_cd = s_co + LP;
-    s_lt = s_cd + LP;
-    s_ok = s_lt + LP;
-  }
-  static constexpr int floats(int LP) { return 3 * LP * VS + 4 * LP; }
-};
 
 // blockDim.x == 4 * LP: thread idx + it * blockDim covers the LP x DH/4 16-byte pieces of a matrix in DH / 16 rounds
 template <int DH>
@@ -95,201 +72,18 @@ __device__ __forceinline__ void stage(const acattn_problem& P, const Staged<DH>&
   }
 }
 
-// One lane's view of its query row: lane = 16 g + c holds, of query row i = 16 qb + c, the keys 16 t + 4 g + r of tile t.
+// RowCore plus what this file alone does with a row
 template <int DH>
-struct Row {
-  static constexpr int KS = DH / 4, VS = DH + 4;
-  const acattn_problem& P;
-  const Staged<DH>& S;
-  int L, c, g, qb, i;
-  bool row_ok, dead, causal, has_drop;
-  size_t rowbase, bh, prow;
-  int hoff;
-  float ao2, ad, sc, scale2, keep_scale;
-  RngKey rkey;
-  float qf[KS], qaf[KS];
+struct Row : RowCore<DH> {
+  using Core = RowCore<DH>;
+  using Core::Core;
+  using Core::KS, Core::VS, Core::P, Core::c, Core::g, Core::i, Core::row_ok, Core::rowbase, Core::hoff;
 
-  __device__ __forceinline__ Row(const acattn_problem& P_, const Staged<DH>& S_, int b, int h, int qb_, int lane)
-      : P(P_), S(S_) {
-    L = P.L;
-    c = lane & 15;
-    g = lane >> 4;
-    qb = qb_;
-    i = 16 * qb + c;
-    row_ok = i < L;
-    causal = P.causal != 0;
-    rowbase = (size_t)b * L;
-    hoff = h * DH;
-    bh = (size_t)b * P.n_heads + h;
-    prow = (bh * L + (row_ok ? i : 0)) * (size_t)L;
-    has_drop = P.p_drop > 0.f;
-    keep_scale = has_drop ? 1.0f / (1.0f - P.p_drop) : 1.0f;
-    scale2 = kLog2e / sqrtf((float)DH);
-    // a row none of whose keys is allowed: the mask's common shift is dropped, the soft-max runs over all L keys
-    const unsigned long long valid = __ballot(lane < L && S.s_ok[lane < L ? lane : 0] != 0.f);
-    const unsigned long long upto = (causal && i < 63) ? ((2ull << i) - 1ull) : ~0ull;
-    dead = !row_ok || (valid & upto) == 0ull;
-    const size_t off = (rowbase + (row_ok ? i : 0)) * P.H + hoff + KS * g;
-    float ao = 0.f, adq = 0.f;
-#pragma unroll
-    for (int s4 = 0; s4 < KS / 4; ++s4) {
-      f4 tq = {0.f, 0.f, 0.f, 0.f}, ta = tq;
-      if (row_ok) {
-        tq = *(const f4*)(P.q + off + 4 * s4);
-        ta = *(const f4*)(P.qa + off + 4 * s4);
-      }
-      const f4 a = *(const f4*)(P.w_order + KS * g + 4 * s4), d = *(const f4*)(P.w_dist + KS * g + 4 * s4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        qf[4 * s4 + e] = tq[e];
-        qaf[4 * s4 + e] = ta[e];
-        ao += tq[e] * a[e];
-        adq += tq[e] * d[e];
-      }
-    }
-    ao2 = -kLog2e * (quad_sum(ao) + P.b_order[0]);
-    ad = quad_sum(adq) + P.b_dist[0];
-    sc = P.scalar[0];
-    rkey = rng_key(P.seed + (P.seed_device ? *P.seed_device : 0ull));
-  }
-
-  // additive mask of tile t in exp2 units: 0 allowed, -10000 log2(e) masked, -inf in the tile padding
-  __device__ __forceinline__ f4 mask4(int t) const {
-    const f4 ok4 = *(const f4*)(S.s_ok + 16 * t + 4 * g);
-    f4 m;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int j = 16 * t + 4 * g + r;
-      const bool allowed = dead || (ok4[r] != 0.f && (!causal || j <= i));
-      m[r] = j >= L ? ACATTN_NEG_INF : (allowed ? 0.f : ACATTN_MASK_FILL * kLog2e);
-    }
-    return m;
-  }
-  // pr = sigmoid(order affine), val = the probability the order term takes the log of (pr for a key after the query,
-  // 1 - pr otherwise; transformer_layers.py:833-845), df = log(|i - j| + 1) - distance affine (:847-855)
-  __device__ __forceinline__ void spatial(int t, f4& pr, f4& val, f4& df) const {
-    const f4 ea = *(const f4*)(S.s_co + 16 * t + 4 * g) + ao2;
-    const f4 cd4 = *(const f4*)(S.s_cd + 16 * t + 4 * g);
-    const int d0 = i - (16 * t + 4 * g);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      pr[r] = fast_rcp(1.0f + ex2(ea[r]));
-      val[r] = (d0 - r < 0) ? pr[r] : 1.0f - pr[r];
-      const int dist = d0 - r < 0 ? r - d0 : d0 - r;
-      df[r] = S.s_lt[dist] - (cd4[r] + ad);  // (dist < LP: both indices are)
-    }
-  }
-  // 4 keys of this row from the row's L floats (NULL = zeros); zeros past L and for rows past L
-  __device__ __forceinline__ f4 load_row(const float* rowp, int t) const {
-    const int j0 = 16 * t + 4 * g;
-    f4 v = {0.f, 0.f, 0.f, 0.f};
-    if (rowp && row_ok && j0 < L) {
-      const float* p = rowp + j0;
-      if (j0 + 3 < L) {
-        v = *(const f4u*)p;
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (j0 + r < L) v[r] = p[r];
-      }
-    }
-    return v;
-  }
-  // the same from a [B,nh,L,L] tensor
-  __device__ __forceinline__ f4 load_seg(const float* t4, int t) const { return load_row(t4 ? t4 + prow : nullptr, t); }
-  __device__ __forceinline__ const float* gate_row() const { return P.gate_logits + (rowbase + (row_ok ? i : 0)) * L; }
-  __device__ __forceinline__ void store_seg(float* t4, int t, const f4 v) const {
-    const int j0 = 16 * t + 4 * g;
-    if (row_ok && j0 < L) {
-      float* p = t4 + prow + j0;
-      if (j0 + 3 < L) {
-        *(f4u*)p = v;
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (j0 + r < L) p[r] = v[r];
-      }
-    }
-  }
-  __device__ __forceinline__ uint32_t load_bits(const uint8_t* k4, int t) const {
-    uint32_t bits = 0xFu;
-    if (k4 && row_ok) {
-      bits = 0;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int j = 16 * t + 4 * g + r;
-        bits |= ((j < L ? k4[prow + j] : (uint8_t)1) ? 1u : 0u) << r;
-      }
-    }
-    return bits;
-  }
-  // the draws of tile t: four normals (zero past L) and the keep bits of P's and M's dropout
-  __device__ __forceinline__ void draws(int t, f4& n, uint32_t& ka, uint32_t& km) const {
-    ka = km = 0xFu;
-    if (P.rng_mode == ACATTN_RNG_COUNTER) {
-      const RngGroup rg = rng_group(rkey, (uint32_t)(bh * L + i), (uint32_t)(4 * t + g), P.p_drop);
-      n = rg.n;
-      if (has_drop) {
-        ka = rg.keep_after;
-        km = rg.keep_mask;
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (16 * t + 4 * g + r >= L) n[r] = 0.f;
-    } else {
-      n = load_seg(P.noise, t);
-      if (has_drop) {
-        ka = load_bits(P.keep_after, t);
-        km = load_bits(P.keep_mask, t);
-      }
-    }
-  }
   // x = C / sqrt(dh) + mask and y = qa.Ka^T / sqrt(dh) + mask, both in exp2 units
   template <int NTB>
   __device__ __forceinline__ void scores(f4 (&x)[NTB], f4 (&y)[NTB]) const {
-    const float nhs2 = -0.5f * (sc * sc);
-#pragma unroll
-    for (int t = 0; t < NTB; ++t) {
-      f4 pr, val, df, lg;
-      spatial(t, pr, val, df);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) lg[r] = __builtin_amdgcn_logf(val[r] + ACATTN_LOG_EPS);
-      x[t] = lg * kLn2 + (df * df) * nhs2;
-      y[t] = f4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int s4 = 0; s4 < KS / 4; ++s4) {
-#pragma unroll
-      for (int t = 0; t < NTB; ++t) {
-        const f4 k4 = *(const f4*)(S.Ks + (16 * t + c) * VS + KS * g + 4 * s4);
-        const f4 a4 = *(const f4*)(S.Kas + (16 * t + c) * VS + KS * g + 4 * s4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          x[t] = mfma16(k4[e], qf[4 * s4 + e], x[t]);
-          y[t] = mfma16(a4[e], qaf[4 * s4 + e], y[t]);
-        }
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < NTB; ++t) {
-      const f4 mk = mask4(t);
-      x[t] = x[t] * scale2 + mk;
-      y[t] = y[t] * scale2 + mk;
-    }
-  }
-  // out[query c][16 dt + 4 g + r] = sum over the keys of w[query c][key] X[key][.], X one of the staged matrices
-  template <int NTB>
-  __device__ __forceinline__ void times_keys(const float* X, const f4 (&w)[NTB], f4 (&o)[DH / 16]) const {
-#pragma unroll
-    for (int dt = 0; dt < DH / 16; ++dt) o[dt] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < NTB; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float* xp = X + (16 * t + 4 * g + r) * VS + c;
-#pragma unroll
-        for (int dt = 0; dt < DH / 16; ++dt) o[dt] = mfma16(xp[16 * dt], w[t][r], o[dt]);
-      }
+    this->template scores_dense<NTB>(x, y);
+    this->template scores_finish<NTB>(x, y);
   }
   // w[query c][key] = sum over the head's columns of X[key][.] d[query c][.]  (d: a [B,L,H] tensor, NULL = zeros)
   template <int NTB>
@@ -310,7 +104,6 @@ struct Row {
       }
     }
   }
-  __device__ __forceinline__ f4 live(const f4 v) const { return row_ok ? v : f4{0.f, 0.f, 0.f, 0.f}; }
 };
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -418,15 +211,6 @@ struct BwdShared {
   }
   static constexpr int floats(int LP) { return 4 * LP * (LP + 4) + 8 * LP + 2 * LP + 3 * LP; }
 };
-
-// sum over the 16 query rows of a block (lanes of equal g), for every lane
-__device__ __forceinline__ float rows16_sum(float v) {
-  v += __shfl_xor(v, 1);
-  v += __shfl_xor(v, 2);
-  v += __shfl_xor(v, 4);
-  v += __shfl_xor(v, 8);
-  return v;
-}
 
 template <int DH, int NTB>
 __device__ __forceinline__ void bwd_block(const acattn_problem& P, const acattn_bwd_io& IO, const Row<DH>& R, const BwdShared& W) {
@@ -656,61 +440,22 @@ __global__ void __launch_bounds__(256) acattn_unnorm_bwd_kernel(const acattn_pro
   }
 }
 
-// The configuration this pair covers (include/acattn.h); `why` receives the limit a problem breaks.
-bool unnorm_supported(const acattn_problem& p, const char** why) {
-  const char* w = nullptr;
-  if (p.B < 1 || p.L < 1 || p.H < 1 || p.n_heads < 1 || p.H % p.n_heads != 0) w = "un-normalised attention: B, L, H, n_heads must be positive and H a multiple of n_heads";
-  else if (p.L > 64) w = "un-normalised attention: sequence length L must be <= 64";
-  else if (p.H / p.n_heads != 16 && p.H / p.n_heads != 32 && p.H / p.n_heads != 64) w = "un-normalised attention: head size must be 16, 32 or 64";
-  else if (!p.adversarial) w = "un-normalised attention: needs the adversarial calibrator (adversarial = 1)";
-  else if (p.combine_option != ACATTN_COMBINE_GATE) w = "un-normalised attention: combine_option must be gate (fixed / annealing are not built)";
-  else if (!p.two_level) w = "un-normalised attention: two_level must be 1 (the one-level form is not built)";
-  else if (p.mask_mode != ACATTN_MASK_STRUCTURED) w = "un-normalised attention: the mask must be structured (key_valid + causal); dense masks are not built";
-  else if (p.rng_mode != ACATTN_RNG_EXPLICIT && p.rng_mode != ACATTN_RNG_COUNTER) w = "un-normalised attention: unknown rng_mode";
-  else if (!(p.p_drop >= 0.f && p.p_drop < 1.f)) w = "un-normalised attention: p_drop must lie in [0, 1)";
-  else if ((int64_t)p.B * p.n_heads * p.L * p.L >= (1LL << 31) || (int64_t)p.B * p.L * p.H >= (1LL << 31)) w = "un-normalised attention: tensors of 2^31 elements or more";
-  if (why) *why = w;
-  return w == nullptr;
-}
-
-const char* unnorm_pointers(const acattn_problem& p) {
-  if (!p.q || !p.k || !p.v || !p.qa || !p.ka) return "un-normalised attention: q, k, v, qa, ka must be non-NULL";
-  if (!p.gate_logits) return "un-normalised attention: combine_option gate needs gate_logits";
-  if (!p.key_valid) return "un-normalised attention: structured mask needs key_valid";
-  if (!p.w_order || !p.b_order || !p.w_dist || !p.b_dist || !p.scalar) return "un-normalised attention: both spatial terms must be present (order and distance affines, scalar)";
-  if (p.rng_mode == ACATTN_RNG_EXPLICIT) {
-    if (!p.noise) return "un-normalised attention: explicit rng mode needs noise";
-    if (p.p_drop > 0.f && (!p.keep_after || !p.keep_mask)) return "un-normalised attention: explicit dropout needs keep_after and keep_mask";
-  }
-  return nullptr;
-}
-
-template <class K, class IO>
-int launch(K kern, size_t lds, int grid, int threads, hipStream_t stream, const acattn_problem& p, const IO& io) {
-  if (lds > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, stream, p, io);
-  return (int)hipGetLastError();
+// The configuration this pair covers (include/acattn.h): the limit a problem breaks, or NULL.
+const char* unnorm_limit(const acattn_problem& p) {
+  const char* w = l64_config(p);
+  return w ? w : l64_sizes(p);
 }
 
 }  // namespace
 
-int acattn_unnorm_supported(const acattn_problem& p) { return unnorm_supported(p, nullptr) ? 1 : 0; }
+int acattn_unnorm_supported(const acattn_problem& p) { return unnorm_limit(p) ? 0 : 1; }
 
 int acattn_launch_unnorm_fwd(const acattn_problem& p, const acattn_fwd_out& o, hipStream_t stream) {
-  const char* why = nullptr;
-  if (!unnorm_supported(p, &why) || (why = unnorm_pointers(p))) {
+  const char* why = unnorm_limit(p);
+  if (!why) why = l64_pointers(p);
+  if (!why) why = l64_fwd_out(o);
+  if (why) {
     acattn_set_error(why);
-    return -1;
-  }
-  if (!o.ctx_attacked || !o.ctx_calibrated || !o.attack_mask) {
-    acattn_set_error("un-normalised attention forward: ctx_attacked, ctx_calibrated and attack_mask must be non-NULL");
-    return -1;
-  }
-  if (o.after_spatial || o.before_spatial || o.perturbed_attention || o.calibrated_attention) {
-    acattn_set_error("un-normalised attention forward: the probability dumps are not built");
     return -1;
   }
   const int nT = (p.L + 15) / 16, LP = 16 * nT, grid = p.B * p.n_heads;
@@ -722,18 +467,9 @@ int acattn_launch_unnorm_fwd(const acattn_problem& p, const acattn_fwd_out& o, h
 }
 
 int acattn_launch_unnorm_bwd(const acattn_problem& p, const acattn_bwd_io& io, hipStream_t stream) {
-  const char* why = nullptr;
-  if (!unnorm_supported(p, &why) || (why = unnorm_pointers(p))) {
-    acattn_set_error(why);
-    return -1;
-  }
-  if (!io.row_stats || !io.attack_mask) why = "un-normalised attention backward: needs the forward's attack_mask and row_stats";
-  else if (!io.dq || !io.dk || !io.dv || !io.dqa || !io.dka) why = "un-normalised attention backward: dq, dk, dv, dqa, dka must be non-NULL";
-  else if (!io.dgate_logits) why = "un-normalised attention backward: gate combine needs dgate_logits";
-  else if (!io.dw_order_part || !io.dw_dist_part || !io.dsmall_part) why = "un-normalised attention backward: parameter partial buffers must be non-NULL";
-  else if (io.part_stride != 0 && io.part_stride < 2 * (p.H / p.n_heads)) why = "un-normalised attention backward: part_stride is smaller than a partial row";
-  else if (io.dgate_summed) why = "un-normalised attention backward: dgate_summed is not built (per-head partials only)";
-  else if (io.dqa2 || io.dka2 || io.d_ctx_calibrated2 || io.d_penalty_part2) why = "un-normalised attention backward: the second cotangent set is not built";
+  const char* why = unnorm_limit(p);
+  if (!why) why = l64_pointers(p);
+  if (!why) why = l64_bwd_io(p, io);
   if (why) {
     acattn_set_error(why);
     return -1;

@@ -358,10 +358,10 @@ class _CalibratedAttention(torch.autograd.Function):
 UNNORM_MAX_L = 64  # csrc/acattn_unnorm.hip holds a query block's row of four key tiles
 
 
-def _check_unnormalised(q, k, v, qa, ka, gate_logits, mask, cfg: AttentionConfig, w_order, w_dist, want_probs: bool):
-    """ValueError naming the limit for everything the un-normalised pair does not take (include/acattn.h:
-    acattn_unnorm_attention_supported); there is no other kernel to fall back to."""
-    what = "attention without re-normalisation (AttentionConfig.renormalise=False)"
+def _check_l64(what: str, max_L: int, q, k, v, qa, ka, gate_logits, mask, cfg: AttentionConfig, w_order, w_dist,
+               want_probs: bool = False, more_tensors=()):
+    """The limits the two L <= 64 cores without re-normalisation share (csrc/acattn_row64.h), as ValueErrors that start
+    with `what`.  `more_tensors`: further (name, tensor) pairs that must live on the GPU."""
     if not cfg.adversarial:
         raise ValueError(f"{what} needs the adversarial calibrator (adversarial=True)")
     if cfg.combine_option != "gate":
@@ -375,13 +375,21 @@ def _check_unnormalised(q, k, v, qa, ka, gate_logits, mask, cfg: AttentionConfig
     if w_order is None or w_dist is None:
         raise ValueError(f"{what} needs both spatial terms (order and distance)")
     for name, t in (("q", q), ("k", k), ("v", v), ("qa", qa), ("ka", ka), ("gate_logits", gate_logits),
-                    ("key_valid", mask.key_valid)):
+                    ("key_valid", mask.key_valid), *more_tensors):
         if t is None or not t.is_cuda:
             raise ValueError(f"{what}: {name} must be a tensor on the GPU (HIP kernels only, no CPU path)")
-    if q.shape[1] > UNNORM_MAX_L:
-        raise ValueError(f"{what} is built for sequence length L <= {UNNORM_MAX_L}, got {q.shape[1]}")
-    if q.shape[2] % cfg.n_heads or q.shape[2] // cfg.n_heads not in (16, 32, 64):
-        raise ValueError(f"{what} is built for head sizes 16, 32 and 64, got hidden {q.shape[2]} / {cfg.n_heads} heads")
+    B, L, H = q.shape
+    if L > max_L:
+        raise ValueError(f"{what} is built for sequence length L <= {max_L}, got {L}")
+    if H % cfg.n_heads or H // cfg.n_heads not in (16, 32, 64):
+        raise ValueError(f"{what} is built for head sizes 16, 32 and 64, got hidden {H} / {cfg.n_heads} heads")
+
+
+def _check_unnormalised(q, k, v, qa, ka, gate_logits, mask, cfg: AttentionConfig, w_order, w_dist, want_probs: bool):
+    """ValueError naming the limit for everything the un-normalised pair does not take (include/acattn.h:
+    acattn_unnorm_attention_supported); there is no other kernel to fall back to."""
+    _check_l64("attention without re-normalisation (AttentionConfig.renormalise=False)", UNNORM_MAX_L, q, k, v, qa, ka,
+               gate_logits, mask, cfg, w_order, w_dist, want_probs)
 
 
 class _UnnormalisedAttention(torch.autograd.Function):
@@ -451,26 +459,10 @@ def _check_timeaware(q, k, v, qa, ka, gate_logits, mask, cfg: AttentionConfig, w
     """ValueError naming the limit for everything csrc/acattn_timeaware.hip does not take (include/acattn.h:
     acattn_timeaware_attention_supported); there is no other kernel to fall back to."""
     what = "time-interval attention (ACTiSASRec)"
-    if not cfg.adversarial:
-        raise ValueError(f"{what} needs the adversarial calibrator (adversarial=True)")
-    if cfg.combine_option != "gate":
-        raise ValueError(f"{what} is built for combine_option 'gate' only, not {cfg.combine_option!r}")
-    if not cfg.two_level:
-        raise ValueError(f"{what} is built for two_level=True only (the one-level form is not)")
-    if not isinstance(mask, StructuredMask):
-        raise ValueError(f"{what} takes a StructuredMask only; dense masks are not built")
-    if w_order is None or w_dist is None:
-        raise ValueError(f"{what} needs both spatial terms (order and distance)")
-    for name, t in (("q", q), ("k", k), ("v", v), ("qa", qa), ("ka", ka), ("gate_logits", gate_logits),
-                    ("key_valid", mask.key_valid), ("pos_k", pos_k), ("pos_v", pos_v), ("time_k.table", time_k.table),
-                    ("time_v.table", time_v.table), ("time index", time_k.index)):
-        if t is None or not t.is_cuda:
-            raise ValueError(f"{what}: {name} must be a tensor on the GPU (HIP kernels only, no CPU path)")
+    _check_l64(what, TIMEAWARE_MAX_L, q, k, v, qa, ka, gate_logits, mask, cfg, w_order, w_dist,
+               more_tensors=(("pos_k", pos_k), ("pos_v", pos_v), ("time_k.table", time_k.table),
+                             ("time_v.table", time_v.table), ("time index", time_k.index)))
     B, L, H = q.shape
-    if L > TIMEAWARE_MAX_L:
-        raise ValueError(f"{what} is built for sequence length L <= {TIMEAWARE_MAX_L}, got {L}")
-    if H % cfg.n_heads or H // cfg.n_heads not in (16, 32, 64):
-        raise ValueError(f"{what} is built for head sizes 16, 32 and 64, got hidden {H} / {cfg.n_heads} heads")
     if time_v.index is not time_k.index and time_v.index.data_ptr() != time_k.index.data_ptr():
         raise ValueError(f"{what}: both time handles must share one index matrix")
     if time_k.index.dtype != torch.int32 or time_k.index.shape != (B, L, L) or not time_k.index.is_contiguous():
