@@ -194,6 +194,10 @@ SYMBOLS = {
     "acattn_full_sort_ce_fwd_pair_workspace_bytes": (C.c_int64, [C.POINTER(CeProblem), C.POINTER(CeProblem)]),
     "acattn_full_sort_ce_fwd_pair": (C.c_int, [C.POINTER(CeProblem), C.POINTER(CeProblem), _f, _f, _f, _f, _f, _f, C.c_void_p]),
     "acattn_full_sort_ce_products": (C.c_int, [C.c_int]),
+    "acattn_full_sort_rank_workspace_bytes": (C.c_int64, [C.POINTER(CeProblem)]),
+    "acattn_full_sort_rank": (C.c_int, [C.POINTER(CeProblem), C.c_int32, _f, _f, _f, C.c_void_p]),
+    "acattn_full_sort_rank_exclude": (C.c_int, [C.POINTER(CeProblem), C.c_int32, _f, _f, C.c_int64, _f, _f, C.c_void_p]),
+    "acattn_full_sort_rank_supported": (C.c_int, [C.c_int32]),
     "acattn_linear_products": (C.c_int, [C.c_int]),
     "acattn_dropout_add_layernorm_fwd": (C.c_int, [C.POINTER(LnProblem), _f, _f, C.c_void_p]),
     "acattn_dropout_add_layernorm_bwd": (C.c_int, [C.POINTER(LnProblem), _f, _f, _f, _f, _f, C.c_void_p]),

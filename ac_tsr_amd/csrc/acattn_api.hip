@@ -316,6 +316,45 @@ int acattn_full_sort_ce_fwd_pair(const acattn_ce_problem* pa, const acattn_ce_pr
 
 int acattn_full_sort_ce_products(int mode) { return acattn_ce_products_choice(mode); }
 
+int acattn_full_sort_rank_supported(int32_t H) { return (H == 64 || H == 128 || H == 256) ? 1 : 0; }
+
+static int check_rank(const acattn_ce_problem* p, int32_t first_item) {
+  if (!p) return fail("rank problem is NULL");
+  if (!acattn_full_sort_rank_supported(p->H)) return fail("unsupported hidden size for the full-sort rank: H must be 64, 128 or 256");
+  if (p->B < 1 || p->N < 1) return fail("full-sort rank: B and N must be positive");
+  if (p->N > (1 << 30)) return fail("full-sort rank: N must not exceed 2^30");
+  if (!p->out || !p->table || !p->target) return fail("full-sort rank: out, table, target must be non-NULL");
+  if (first_item < 0 || first_item >= p->N) return fail("full-sort rank: first_item must lie in [0, N)");
+  return 0;
+}
+
+int64_t acattn_full_sort_rank_workspace_bytes(const acattn_ce_problem* p) {
+  if (!p || !acattn_full_sort_rank_supported(p->H) || p->B < 1 || p->N < 1 || p->N > (1 << 30)) return -1;
+  return acattn_rank_ws_bytes(*p);
+}
+
+int acattn_full_sort_rank(const acattn_ce_problem* p, int32_t first_item, void* workspace, int32_t* rank, float* target_score,
+                          void* stream) {
+  if (int rc = check_rank(p, first_item)) return rc;
+  if (!workspace || !rank || !target_score) return fail("full-sort rank: workspace, rank, target_score must be non-NULL");
+  const int rc = acattn_launch_rank(*p, first_item, workspace, rank, target_score, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
+int acattn_full_sort_rank_exclude(const acattn_ce_problem* p, int32_t first_item, const int64_t* pair_row,
+                                  const int64_t* pair_item, int64_t n_pairs, const float* target_score, int32_t* rank,
+                                  void* stream) {
+  if (int rc = check_rank(p, first_item)) return rc;
+  if (!rank || !target_score) return fail("full-sort rank: rank, target_score must be non-NULL");
+  if (n_pairs < 0) return fail("full-sort rank: n_pairs must not be negative");
+  if (n_pairs > 0 && (!pair_row || !pair_item)) return fail("full-sort rank: pair_row, pair_item must be non-NULL when n_pairs > 0");
+  if (n_pairs == 0) return 0;
+  const int rc = acattn_launch_rank_exclude(*p, first_item, pair_row, pair_item, n_pairs, target_score, rank, (hipStream_t)stream);
+  if (rc > 0) snprintf(g_err, sizeof(g_err), "HIP launch failed: %s", hipGetErrorString((hipError_t)rc));
+  return rc;
+}
+
 int acattn_linear_products(int mode) { return acattn_linear_products_choice(mode); }
 
 static int check_ln(const acattn_ln_problem* p) {

@@ -410,6 +410,11 @@ int64_t acattn_ce_pair_ws_bytes(const acattn_ce_problem& pa, const acattn_ce_pro
 int acattn_launch_ce_fwd_pair(const acattn_ce_problem& pa, const acattn_ce_problem& pc, void* ws, float* lse_a, float* row_loss_a,
                               float* dir_a, float* lse_c, float* row_loss_c, hipStream_t stream);
 int acattn_ce_products_choice(int mode);
+// acattn_rank.hip: full-sort evaluation, the targets' ranks
+int64_t acattn_rank_ws_bytes(const acattn_ce_problem& p);
+int acattn_launch_rank(const acattn_ce_problem& p, int first_item, void* ws, int* rank, float* target_score, hipStream_t stream);
+int acattn_launch_rank_exclude(const acattn_ce_problem& p, int first_item, const int64_t* pair_row, const int64_t* pair_item,
+                               int64_t n_pairs, const float* target_score, int* rank, hipStream_t stream);
 int acattn_linear_products_choice(int mode);
 int acattn_launch_dense_ce_fwd(const float* logits, int64_t rows, int64_t N, const int64_t* target, float* lse, float* row_loss,
                                hipStream_t stream);

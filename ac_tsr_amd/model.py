@@ -100,6 +100,28 @@ class SequentialRecommender(nn.Module):
         gather_index = gather_index.view(-1, 1, 1).expand(-1, -1, output.shape[-1])
         return output.gather(dim=1, index=gather_index).squeeze(1)
 
+    def _target_ranks(self, output, table, interaction, target, history_index, n_items=None, row_term=None):
+        """rank.Ranks of `target` (default interaction[ITEM_ID]) under output @ table[:n_items].T, the padding item and the
+        pairs of `history_index` left out (recbole/trainer/trainer.py:941-944), None for output None.  The [B, N] scores
+        are not formed where ac_tsr_amd.rank has kernels (CUDA, hidden size 64 / 128 / 256); elsewhere they are, as
+        full_sort_predict forms them.  `row_term` [B] is added to the returned target scores: a per-row constant moves
+        every score of the row alike and never enters the count."""
+        if output is None:
+            return None
+        from . import rank as R
+        with torch.no_grad():
+            target = interaction[self.ITEM_ID] if target is None else target
+            target = target.to(output.device).long().contiguous()
+            n = table.shape[0] if n_items is None else n_items
+            if R.supported(output.shape[1]) and output.is_cuda and table.is_cuda and output.dtype == torch.float32:
+                res = R.full_sort_ranks(output.contiguous(), table.contiguous(), target, n_items=n, first_item=1,
+                                        history_index=history_index)
+            else:
+                res = R.dense_ranks(torch.matmul(output, table[:n].transpose(0, 1)), target, 1, history_index)
+            if row_term is not None:
+                res = R.Ranks(res.rank, res.target_score + row_term)
+            return res
+
     def get_attention_mask(self, item_seq, bidirectional=False):
         """Dense additive mask exactly as the reference builds it (abstract_recommender.py:136-143)."""
         attention_mask = (item_seq != 0)
@@ -265,6 +287,13 @@ class ACSASRec(SequentialRecommender):
         scores = torch.matmul(calibrated_output, self.item_embedding.weight.transpose(0, 1))
         return None, scores
 
+    @torch.no_grad()
+    def full_sort_rank(self, interaction, target=None, history_index=None):
+        """(None, rank.Ranks of the calibrated branch): what full_sort_predict's scores give the evaluator for one
+        positive per row, without the scores (SequentialRecommender._target_ranks)."""
+        _, calibrated_output, _ = self.forward(interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN])
+        return None, self._target_ranks(calibrated_output, self.item_embedding.weight, interaction, target, history_index)
+
 
 class ACSSEPT(SequentialRecommender):
     """recbole/model/sequential_recommender/acssept.py:21-228: SASRec personalised with a user embedding that is concatenated
@@ -398,6 +427,17 @@ class ACSSEPT(SequentialRecommender):
         table, Di = self.item_embedding.weight, self.item_hidden_size
         score = lambda out: torch.matmul(out[:, :Di], table.transpose(0, 1)) + self._user_test_term(out, user_id).unsqueeze(1)
         return score(attacked_output), score(calibrated_output)
+
+    @torch.no_grad()
+    def full_sort_rank(self, interaction, target=None, history_index=None):
+        """(attacked, calibrated) rank.Ranks.  The item half out[:, :Di] is ranked against the item table; the user term is
+        the same for every item of a row, so it is added to the returned target scores only."""
+        user_id = interaction[self.USER_ID]
+        attacked_output, calibrated_output, _ = self.forward(interaction[self.ITEM_SEQ], interaction[self.ITEM_SEQ_LEN], user_id)
+        table, Di = self.item_embedding.weight, self.item_hidden_size
+        ranks = lambda out: self._target_ranks(out[:, :Di], table, interaction, target, history_index,
+                                               row_term=self._user_test_term(out, user_id))
+        return ranks(attacked_output), ranks(calibrated_output)
 
 
 class ACTiSASRec(SequentialRecommender):
@@ -536,6 +576,14 @@ class ACTiSASRec(SequentialRecommender):
         attacked_output, calibrated_output, _ = self._outputs(interaction, _rnds=_rnds)
         table = self.item_embedding.weight.transpose(0, 1)
         return torch.matmul(attacked_output, table), torch.matmul(calibrated_output, table)
+
+    @torch.no_grad()
+    def full_sort_rank(self, interaction, target=None, history_index=None):
+        """(attacked, calibrated) rank.Ranks of the scores full_sort_predict forms (SequentialRecommender._target_ranks)."""
+        attacked_output, calibrated_output, _ = self._outputs(interaction)
+        table = self.item_embedding.weight
+        return (self._target_ranks(attacked_output, table, interaction, target, history_index),
+                self._target_ranks(calibrated_output, table, interaction, target, history_index))
 
 
 class AcBERT4Rec(SequentialRecommender):
@@ -757,6 +805,17 @@ class AcBERT4Rec(SequentialRecommender):
         attacked_scores = torch.matmul(attacked_output.squeeze(1), test_items_emb.transpose(0, 1))
         scores = torch.matmul(calibrated_output.squeeze(1), test_items_emb.transpose(0, 1))
         return attacked_scores, scores
+
+    @torch.no_grad()
+    def full_sort_rank(self, interaction, target=None, history_index=None):
+        """(attacked, calibrated) rank.Ranks over the first n_items rows of the table: the mask token's row behind them
+        never takes part (SequentialRecommender._target_ranks)."""
+        item_seq_len = interaction[self.ITEM_SEQ_LEN]
+        item_seq = self.reconstruct_test_data(interaction[self.ITEM_SEQ], item_seq_len)
+        attacked_output, calibrated_output, _ = self.forward(item_seq, _rows=item_seq_len.view(-1, 1))
+        table = self.item_embedding.weight
+        ranks = lambda out: self._target_ranks(out.squeeze(1), table, interaction, target, history_index, n_items=self.n_items)
+        return ranks(attacked_output), ranks(calibrated_output)
 
 
 class _BPRLoss(nn.Module):

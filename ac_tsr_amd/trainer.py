@@ -379,6 +379,53 @@ class AttackSASRecTrainer:
         scores[:, 0] = -float('inf')
         return scores
 
+    def _config_value(self, key):
+        """config[key], None for a missing key or no config."""
+        try:
+            return self.config[key] if self.config is not None else None
+        except KeyError:
+            return None
+
+    @torch.no_grad()
+    def evaluate(self, eval_data, topk=None, metrics=None):
+        """The evaluation loop of the reference (trainer.py:965-1018) for full-sort, leave-one-out data: batches
+        (interaction, history_index, positive_u, positive_i) with one positive per row, positive_u == arange(rows).  Each
+        batch yields the targets' ranks (model.full_sort_rank: no [B, n_items] scores where the kernels apply); the ranks
+        stay on the device until the loop ends, then metrics.topk_metrics turns them into the reference's result dict
+        ('mrr@10', ...).  `topk` / `metrics` default to the config's, then to [10] and Recall, MRR, NDCG, Hit, Precision.
+        Several positives per row, or metrics that need the recommended lists: evaluate_scores and the reference's
+        collector."""
+        from . import metrics as M
+        topk = topk or self._config_value('topk') or [10]
+        topk = [topk] if isinstance(topk, int) else list(topk)
+        metrics = metrics or self._config_value('metrics') or M.DEFAULT_METRICS
+        metrics = [metrics] if isinstance(metrics, str) else list(metrics)
+        M.check_metric_names(metrics)
+        self.model.eval()
+        ranks = []
+        for interaction, history_index, positive_u, positive_i in eval_data:
+            positive_u, positive_i = torch.as_tensor(positive_u).reshape(-1), torch.as_tensor(positive_i).reshape(-1)
+            interaction = {k: v.to(self.device) for k, v in interaction.items()} if isinstance(interaction, dict) \
+                else interaction.to(self.device)
+            rows = interaction[self.model.ITEM_SEQ].shape[0]
+            if positive_u.numel() != rows or positive_i.numel() != rows or \
+                    not torch.equal(positive_u.cpu(), torch.arange(rows, dtype=positive_u.dtype)):
+                raise NotImplementedError("evaluate() ranks one positive per row (positive_u == arange(rows), leave-one-out "
+                                          "evaluation); for other data take the dense scores from evaluate_scores")
+            _, calibrated = self.model.full_sort_rank(interaction, target=positive_i.to(self.device), history_index=history_index)
+            ranks.append(calibrated.rank)
+        if not ranks:
+            return None  # (trainer.py:979-980)
+        decimal_place = self._config_value('metric_decimal_place')
+        return M.topk_metrics(torch.cat(ranks), topk, metrics, 4 if decimal_place is None else decimal_place)
+
+    def _valid_epoch(self, valid_data):
+        """(valid_score, valid_result) as trainer.py:695-708: the result of evaluate() and its entry `valid_metric`
+        (config, default 'MRR@10')."""
+        result = self.evaluate(valid_data)
+        valid_metric = (self._config_value('valid_metric') or 'MRR@10').lower()
+        return result[valid_metric], result
+
 
 class ACSASRecTrainer(AttackSASRecTrainer):
     """Alias kept by the reference (trainer.py:1042-1044)."""

@@ -261,6 +261,38 @@ int acattn_full_sort_ce_bwd(const acattn_ce_problem* p, const float* lse, const 
 #define ACATTN_CE_PRODUCTS_ALL 2
 int acattn_full_sort_ce_products(int mode);
 
+/* Full-sort evaluation for leave-one-out data (one positive per row) without the [B, N] scores (acattn_rank.hip):
+ *   rank[b] = 1 + #{ j in [first_item, N), j != target[b] : out_b . table_j ahead of out_b . table_target(b) }
+ * Replaces, per evaluation batch, the dense scores of _full_sort_batch_eval and their masking
+ * (recbole/trainer/trainer.py:926-945: full_sort_predict, scores[:, 0] = -inf, scores[history_index] = -inf) and the
+ * top-K selection and gather of the collector (recbole/evaluator/collector.py:141-153): Hit / Recall / MRR / NDCG /
+ * Precision of a row with one positive are functions of that rank alone.
+ * `p` is read as for the cross-entropy: out [B,H], table [>= N,H], target [B]; N = the table rows that take part (a
+ * model whose table carries a mask token behind the items passes n_items).  first_item = 1 leaves the padding item out
+ * (trainer.py:942), 0 ranks every row of the table.
+ * "Ahead" is !(s_j <= s_t) on exact-fp32 scores that have the same bits wherever they are formed: an item whose table
+ * row equals the target's bit for bit is not ahead, a NaN item score is (torch.topk's order).  rank[b] = 0 marks an
+ * invalid row: a target outside [first_item, N) (never read out of bounds) or a NaN target score; target_score[b] is NaN
+ * for the former.  No float atomics; every output element has one writer; results do not depend on launch order.
+ * `workspace`: acattn_full_sort_rank_workspace_bytes bytes (-1 for an unsupported problem), contents irrelevant.
+ * Validation (before any HIP call, -1 and acattn_last_error): H not in {64, 128, 256}, B or N < 1, NULL pointers,
+ * first_item outside [0, N). */
+int64_t acattn_full_sort_rank_workspace_bytes(const acattn_ce_problem* p);
+int acattn_full_sort_rank(const acattn_ce_problem* p, int32_t first_item, void* workspace, int32_t* rank, float* target_score,
+                          void* stream);
+
+/* History exclusion behind acattn_full_sort_rank (trainer.py:943-944, scores[history_index] = -inf): n_pairs UNIQUE
+ * (pair_row[i], pair_item[i]) pairs become inadmissible -- each pair's score is formed by the routine that formed the
+ * targets' and, where the sweep counted it as ahead, takes 1 off rank[row] (integer atomics: deterministic).  Ignored:
+ * rows outside [0, B), items outside [first_item, N), the target itself, rows with rank 0.  target_score and rank are
+ * acattn_full_sort_rank's outputs for the same `p` and first_item.  n_pairs = 0 launches nothing. */
+int acattn_full_sort_rank_exclude(const acattn_ce_problem* p, int32_t first_item, const int64_t* pair_row,
+                                  const int64_t* pair_item, int64_t n_pairs, const float* target_score, int32_t* rank,
+                                  void* stream);
+
+/* 1 for the hidden sizes acattn_full_sort_rank takes (64, 128, 256), else 0. */
+int acattn_full_sort_rank_supported(int32_t H);
+
 /* y = LayerNorm(dropout(z) + residual) * gamma + beta   (the tail of both sub-blocks
  * of a layer -- recbole/model/layers.py:681-683 and :794-796).  Rows of H in {64, 128, 256} floats. */
 #define ACATTN_LN_BWD_GRID 512 /* workgroups of the backward == rows of its dgamma/dbeta partial buffer */
